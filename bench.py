@@ -15,9 +15,15 @@ run directly with --gpus N > 1 it starts N fresh rank processes itself (before
 any GPU call), relays rank 0's JSON line and exits with the worst rank status.
 
 Prints ONE JSON line on rank 0 (contract in the task statement), with a
-`roofline` object for the dominant kernel (HIP events on the launch stream)
-and a `cpu_baseline` timed on this host (the reference ec-cpp built in
-oracle/_ref if present, else the C restatement).
+`roofline` object for the dominant kernel (HIP events on the launch stream).
+
+A plain run sets up, warms up, times the steps, checks the round trip of the
+last step, writes the outputs (--dump-outputs) and prints the line.  --full adds
+every other measurement, each a run of its own after the timed steps: the
+measured device copy / fill bandwidth (`roofline.measured`), the benchmark/
+size sweep (`sizes`), the host-resident `e2e` block, the `cpu_baseline` timed
+on this host (the reference ec-cpp built in oracle/_ref if present, else the C
+restatement) and, for N > 1, the RCCL scatter / gather.
 """
 from __future__ import annotations
 
@@ -501,6 +507,48 @@ def e2e(args, nv, dev, dist, world, rank, cdev):
             "config2": cfg2, "config5_mixed": cfg5}, ok and ok5
 
 
+# --dump-outputs: elements kept of each output of the last timed step (as
+# float32: 16 + 16 + 8 MB at most)
+DUMP_CAP = {"shards": 4 << 20, "error_locator": 2 << 20, "payloads": 4 << 20}
+
+
+def _dump_pick(name, total):
+    """Flat element indices of output `name` that are written out: all of them
+    up to DUMP_CAP[name], else a fixed sample (splitmix64, seeded by the name:
+    the same indices in every run and every build), ascending."""
+    cap = DUMP_CAP[name]
+    if total <= cap:
+        return None
+    seed = int.from_bytes(name.encode()[:8].ljust(8, b"\0"), "little")
+    return np.sort((synth.splitmix64_words(seed, cap) % np.uint64(total)).astype(np.int64))
+
+
+def dump_outputs(out_dir, rank, d_sh, sl, d_el, d_out):
+    """What a caller of the timed path holds after its last step, as
+    <name>.npy (float32, exact for the byte / uint16 values): `shards`
+    [batch][n_validators][shard_len] of encode (the row padding up to the
+    stride is no output and is left out), `error_locator` [batch][n] log
+    multipliers, `payloads` [batch][shard_len * k] of reconstruct.  Arrays above
+    DUMP_CAP elements are sampled (_dump_pick).  Rank r > 0 of a multi-GPU run
+    writes <name>_rank<r>.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    ss = d_sh.shape[2]
+    tag = "" if rank == 0 else f"_rank{rank}"
+    for name, t, width, stride in (("shards", d_sh, sl, ss),
+                                   ("error_locator", d_el, d_el.shape[1], d_el.shape[1]),
+                                   ("payloads", d_out, d_out.shape[1], d_out.shape[1])):
+        rows = t.numel() // stride
+        pick = _dump_pick(name, rows * width)
+        if pick is None:
+            arr = t.reshape(rows, stride)[:, :width].reshape(t.shape[:-1] + (width,))
+        else:
+            off = torch.from_numpy(pick // width * stride + pick % width).to(t.device)
+            arr = t.reshape(-1)[off]
+        if arr.dtype == torch.int16:  # the uint16 multipliers, held in torch's int16
+            arr = arr.to(torch.int32) & 0xFFFF
+        np.save(os.path.join(out_dir, f"{name}{tag}.npy"), arr.to(torch.float32).cpu().numpy())
+
+
 def scatter_gather(dist, rank, world, dev, B, plen, d_pay, d_out, step_s, timeout_s,
                    on_timeout=None):
     """SURVEY.md §8e / north_star: the batch starts on GPU0 and the decoded
@@ -681,7 +729,20 @@ def main():
     ap.add_argument("--graph", action="store_true",
                     help="time K replays of one captured hipGraph step (ECCR_AMD_*_ws calls on "
                          "caller-owned scratch) instead of K eager steps")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other measurement: the measured "
+                         "device bandwidth, the size sweep, the e2e block, the CPU baseline and "
+                         "(N > 1) the scatter / gather; each can still be switched off by its "
+                         "own option.  Without --full none of them runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the outputs of the last one (shards, "
+                         "error_locator, payloads; a fixed sample of the large ones) to "
+                         "DIR/<name>.npy as float32")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:  # a plain run: the headline measurement alone
+        args.sweep, args.no_e2e, args.no_cpu_baseline, args.no_scatter = "none", True, True, True
     args.sweep_sizes = (() if args.sweep == "none" else BENCH_SIZES if args.sweep == "bench"
                         else tuple(int(x) for x in args.sweep.split(",")))
 
@@ -729,8 +790,8 @@ def main():
         d_pay[c0:c0 + 256] = synth.payloads_torch(seeds[c0:c0 + 256], plen, device=dev)
     d_pres = torch.from_numpy(synth.present_masks([10**6 + s for s in seeds], nv, cnt, n)).to(dev)
     d_sh = torch.empty((B, nv, ss), dtype=torch.uint8, device=dev)
-    d_el = torch.empty((B, n), dtype=torch.int16, device=dev)
-    d_out = torch.empty((B, sl * k), dtype=torch.uint8, device=dev)
+    d_el = torch.zeros((B, n), dtype=torch.int16, device=dev)
+    d_out = torch.zeros((B, sl * k), dtype=torch.uint8, device=dev)
     stream = torch.cuda.current_stream(dev)
 
     ev = []
@@ -796,6 +857,8 @@ def main():
 
     # sanity: the last step's reconstruction equals the payloads (round trip)
     ok = bool(torch.equal(d_out[:, :plen], d_pay))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, d_sh, sl, d_el, d_out)
 
     ms = lambda a, b: np.mean([x[a].elapsed_time(x[b]) for x in ev])  # noqa: E731
     t_enc, t_loc, t_rec = ms(0, 1), ms(1, 2), ms(2, 3)
@@ -807,7 +870,7 @@ def main():
     achieved = b_dom / (t_dom * 1e-3)
 
     traffic, traffic_src = pmc_traffic(dom, nv, plen, cnt, B)
-    bw = device_bandwidth(dev)
+    bw = device_bandwidth(dev) if args.full else None
     mul_enc, mul_rec = gf_mul_counts(nv, n, k, cnt)
     pieces, cols = -(-plen // (2 * k)), sl // 2
     total_bytes = world * B * plen * args.steps
@@ -835,7 +898,8 @@ def main():
                      "traffic": traffic, "traffic_source": traffic_src,
                      "bytes_per_launch": b_dom, "avg_launch_ms": round(t_dom, 4),
                      "issue": sq_issue(dom, nv),
-                     "measured": dict(bw, frac_of_copy=round(achieved / (bw["copy_GBps"] * 1e9), 4))},
+                     "measured": (dict(bw, frac_of_copy=round(achieved / (bw["copy_GBps"] * 1e9), 4))
+                                  if bw else None)},
         # secondary figure: the REFERENCE algorithm's GF(2^16)
         # multiplies (additive_fft.hpp:99-141) per second of our kernel time.
         # Not a ceiling: the kernels run fewer multiplies than the reference

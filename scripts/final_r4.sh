@@ -7,7 +7,7 @@ set -u
 export TMPDIR=/tmp
 O=${O:-gpurun_out/r4final}; mkdir -p $O/nv_sweep
 echo "== driver bench ($(date +%T))"
-timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err \
+timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver.json 2> $O/bench_driver.err \
   || { tail -5 $O/bench_driver.err; exit 1; }
 echo "== nv sweep ($(date +%T))"
 for nv in 600 765 1024 1025 1500 2500 3069 4096; do

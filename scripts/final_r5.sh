@@ -14,7 +14,7 @@ if [ "${PART:-a}" = a ]; then
     || { tail -30 $O/pytest_gpu.log; exit 1; }
   tail -1 $O/pytest_gpu.log
   step "driver bench"
-  timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err \
+  timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver.json 2> $O/bench_driver.err \
     || { tail -5 $O/bench_driver.err; exit 1; }
   step rocprof
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- \

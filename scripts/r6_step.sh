@@ -13,7 +13,7 @@ if [ -z "${NOTEST:-}" ]; then
   stop_on_fault $rc pytest
 fi
 if [ -n "${BENCH:-}" ]; then
-  timeout -k 10 300 python bench.py ${BENCHARGS:-} > $O/bench_default.json 2> $O/bench_default.err
+  timeout -k 10 300 python bench.py --full ${BENCHARGS:-} > $O/bench_default.json 2> $O/bench_default.err
   rc=$?; stop_on_fault $rc bench
   python3 -c "
 import json; d=json.loads(open('$O/bench_default.json').read().strip().splitlines()[-1])

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Print the headline and the benchmark/ size sweep of a bench.py JSON line."""
+"""Print the headline and the benchmark/ size sweep of a `bench.py --full` JSON line."""
 import json
 import sys
 

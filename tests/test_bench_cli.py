@@ -47,6 +47,41 @@ def test_launched_ranks_failure_propagates():
     assert not any(l.startswith("{") for l in r.stdout.splitlines())
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs on CPU tensors: small outputs are written whole, without
+    the shard rows' padding; outputs above the cap as a fixed sample of the
+    valid elements (the same indices in every run), all as float32."""
+    import numpy as np
+    import torch
+    import bench
+    B, nv, sl, ss, n, ob = 3, 4, 6, 8, 4, 12
+    d_sh = torch.full((B, nv, ss), 255, dtype=torch.uint8)
+    valid = torch.arange(B * nv * sl, dtype=torch.int64).remainder(251).to(torch.uint8).reshape(B, nv, sl)
+    d_sh[:, :, :sl] = valid
+    d_el = (torch.arange(B * n, dtype=torch.int32) * 2731 - 16000).to(torch.int16).reshape(B, n)
+    d_out = torch.arange(B * ob, dtype=torch.int64).remainder(256).to(torch.uint8).reshape(B, ob)
+    bench.dump_outputs(str(tmp_path / "whole"), 0, d_sh, sl, d_el, d_out)
+    got = {f.name: np.load(f) for f in (tmp_path / "whole").iterdir()}
+    assert sorted(got) == ["error_locator.npy", "payloads.npy", "shards.npy"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["shards.npy"], valid.numpy().astype(np.float32))
+    assert np.array_equal(got["error_locator.npy"],  # uint16 values (held as int16)
+                          d_el.numpy().view(np.uint16).astype(np.float32))
+    assert got["error_locator.npy"].min() >= 0 and got["error_locator.npy"].max() > 32767
+    assert np.array_equal(got["payloads.npy"], d_out.numpy().astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_CAP", {"shards": 16, "error_locator": 5, "payloads": 7})
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), 1, d_sh, sl, d_el, d_out)
+    a = {f.name: np.load(f) for f in (tmp_path / "a").iterdir()}
+    assert sorted(a) == ["error_locator_rank1.npy", "payloads_rank1.npy", "shards_rank1.npy"]
+    assert [a[x].shape for x in sorted(a)] == [(5,), (7,), (16,)]
+    for name, arr in a.items():
+        assert arr.dtype == np.float32 and np.array_equal(arr, np.load(tmp_path / "b" / name))
+    pick = bench._dump_pick("shards", B * nv * sl)
+    assert np.all(np.diff(pick) >= 0) and 0 <= pick[0] and pick[-1] < B * nv * sl
+    assert np.array_equal(a["shards_rank1.npy"], valid.numpy().reshape(-1)[pick].astype(np.float32))
+
+
 def test_parent_signal_terminates_ranks(tmp_path):
     """killing only the launching parent (SIGTERM to its pid) must
     not leave its rank processes running (they would keep their GPUs).  The

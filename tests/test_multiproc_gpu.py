@@ -38,7 +38,7 @@ def _torchrun(script_args, timeout=300):
 
 def test_bench_two_ranks_share_gpu():
     r, line = _torchrun(["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1",
-                         "--batch", "48", "--payload", "100000", "--no-cpu-baseline",
+                         "--batch", "48", "--payload", "100000", "--full", "--no-cpu-baseline",
                          "--e2e-batch", "8", "--e2e-per-size", "2", "--e2e-reps", "1"])
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     assert line is not None and line["roundtrip_ok"], line
@@ -88,7 +88,7 @@ def test_bench_e2e_block_one_rank():
     (PCIe-inclusive) rates, config 2 shape and the config-5 size mix, each next
     to the PCIe bound from this box's measured pinned copy rates."""
     cmd = [sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "32",
-           "--payload", "1000000", "--no-cpu-baseline", "--sweep", "none",
+           "--payload", "1000000", "--full", "--no-cpu-baseline", "--sweep", "none",
            "--e2e-batch", "16", "--e2e-per-size", "2", "--e2e-reps", "1"]
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
@@ -106,3 +106,41 @@ def test_bench_e2e_block_one_rank():
         # the bound is a bound: no measured rate above it (5% timing slack)
         assert 0 < e[leg]["frac_of_pcie_bound"] <= 1.05, e[leg]
     assert e["config2"]["batch_per_gpu"] == 16 and e["config5_mixed"]["payloads"] == 12
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain run measures the headline alone (none of the --full blocks in its
+    line), and --dump-outputs writes what the last timed step computed: float32
+    arrays, the shards without their row padding, and payloads that are the
+    synthetic inputs again (seed = payload index: the same in every run)."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "erasure-coding-crust_amd"))
+    import synth
+    B, plen, nv = 5, 10_001, 1024
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--batch", str(B), "--payload", str(plen), "--dump-outputs", str(tmp_path / "out")]
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    r = subprocess.run(["timeout", "-k", "10", "120"] + cmd, cwd=ROOT, env=env,
+                       capture_output=True, text=True)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["roundtrip_ok"] and line["steps"] == 3 and line["ms_per_step"] > 0, line
+    assert line["value"] > 0 and line["unit"] == "GiB/s" and line["dtype"] == "u16", line
+    for key in ("sizes", "e2e", "cpu_baseline", "scatter_gather"):
+        assert key not in line, key
+    assert line["roofline"]["measured"] is None
+    got = {f.name: np.load(f) for f in (tmp_path / "out").iterdir()}
+    assert sorted(got) == ["error_locator.npy", "payloads.npy", "shards.npy"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    k, sl = 256, 40  # n_validators 1024: k = 256 data shards of ceil(10001 / 512) * 2 bytes
+    assert got["shards.npy"].shape == (B, nv, sl)
+    assert got["error_locator.npy"].shape == (B, 1024)
+    assert got["payloads.npy"].shape == (B, sl * k)
+    want = np.stack([synth.payload(b, plen) for b in range(B)]).astype(np.float32)
+    assert np.array_equal(got["payloads.npy"][:, :plen], want)
+    assert not got["payloads.npy"][:, plen:].any()  # zero-padded past the payload
+    # systematic code: the first k shards are the payload's 2-byte symbols, dealt round-robin
+    data = got["shards.npy"][:, :k].reshape(B, k, sl // 2, 2).transpose(0, 2, 1, 3).reshape(B, -1)
+    assert np.array_equal(data[:, :plen], want)
