@@ -656,6 +656,31 @@ NPRSResult ECCR_AMD_reconstruct_batch(unsigned long nv, const uint8_t *d_shards,
                                              nullptr, batch, d_out, ostride, stream);
 }
 
+const char *ECCR_AMD_encode_kernel(unsigned long nv, const uint8_t *d_payloads, unsigned long plen,
+                                   unsigned long pstride, unsigned long batch,
+                                   const uint8_t *d_shards, unsigned long sstride) {
+  CodeParams p;
+  if (code_params(nv, &p) != ParamError::kOk || plen == 0) return nullptr;
+  if (sstride < shard_len(p.k, plen) || pstride < plen) return nullptr;
+  return kernel_name(choose_encode(p, plen, pstride, batch, reinterpret_cast<uintptr_t>(d_payloads),
+                                   reinterpret_cast<uintptr_t>(d_shards), sstride));
+}
+
+const char *ECCR_AMD_reconstruct_kernel(unsigned long nv, const uint8_t *d_shards,
+                                        unsigned long slen, unsigned long sstride,
+                                        const uint8_t *d_present, const uint16_t *d_err_log,
+                                        unsigned long batch, const uint8_t *d_out,
+                                        unsigned long ostride) {
+  CodeParams p;
+  if (code_params(nv, &p) != ParamError::kOk || slen % 2 != 0) return nullptr;
+  if (sstride < slen || ostride < slen * p.k) return nullptr;
+  const ReconOverrides &o = recon_overrides();
+  return kernel_name(choose_reconstruct(
+      p, slen, sstride, batch, reinterpret_cast<uintptr_t>(d_shards),
+      reinterpret_cast<uintptr_t>(d_present), reinterpret_cast<uintptr_t>(d_err_log),
+      reinterpret_cast<uintptr_t>(d_out), ostride, o.waves8, o.force_packed));
+}
+
 NPRSResult ECCR_AMD_locator_cache_stats(unsigned long *hits, unsigned long *misses) {
   DeviceState *d = device_state();
   if (!d) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);

@@ -18,8 +18,6 @@
 //     each lane writes 8 contiguous bytes of a 512-byte output row.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "dec_n1024_common.hpp"
 #include "ec_device.hpp"
 #include "ec_kernels.hpp"
@@ -613,29 +611,19 @@ __global__ void __launch_bounds__(THREADS) reconstruct_n1024(
 
 bool n1024_applicable(const CodeParams &p) { return p.n == 1024 && p.k == 256; }
 
-// packed tiles: fewer columns per payload than a tile, or a shard pitch / base
-// the 16-B row loads cannot take (any even pitch and base then)
-bool n1024_packed(size_t slen, uintptr_t sh, size_t sstride) {
-  return slen / 2 < size_t(COLS) || sh % 16 != 0 || sstride % 16 != 0;
-}
+static_assert(size_t(COLS) == kN1024Cols, "choose_reconstruct tests this tile");
 
-hipError_t launch_reconstruct_n1024(const CodeParams &p, const DevTables &t,
+// packed (choose_reconstruct: fewer columns per payload than a tile, a shard
+// pitch / base the 16-B row loads cannot take, or the experiment override):
+// any even pitch and base, ncols4 * batch + COLS < 2^32
+hipError_t launch_reconstruct_n1024(const CodeParams &p, const DevTables &t, bool packed,
                                     const uint8_t *d_shards, size_t slen, size_t sstride,
                                     const uint8_t *d_present, const uint16_t *d_err_log,
                                     const uint32_t *d_pattern,
                                     size_t batch, uint8_t *d_out, size_t ostride, void *scratch,
                                     hipStream_t s) {
   int cus = 0;
-  // ECCR_AMD_RECON_PACKED=1 (experiments, scripts/ab_*): packed at every size
-  static const bool force_packed = [] {
-    const char *e = std::getenv("ECCR_AMD_RECON_PACKED");
-    return e && e[0] == '1';
-  }();
-  const bool packed = force_packed || n1024_packed(slen, reinterpret_cast<uintptr_t>(d_shards), sstride);
   const size_t ncols4 = (slen / 2 + 3) / 4 * 4;
-  if (packed && (reinterpret_cast<uintptr_t>(d_shards) % 2 != 0 || sstride % 2 != 0 ||
-                 ncols4 * batch + COLS >= (size_t(1) << 32)))
-    return hipErrorInvalidValue;
   const void *fn = packed ? reinterpret_cast<const void *>(&reconstruct_n1024<true>)
                           : reinterpret_cast<const void *>(&reconstruct_n1024<false>);
   if (const hipError_t e = prepare_kernel(fn, LDS_BYTES, &cus); e != hipSuccess) return e;

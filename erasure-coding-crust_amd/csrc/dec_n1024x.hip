@@ -552,6 +552,8 @@ __global__ void __launch_bounds__(THREADS) reconstruct_n1024x(
 size_t n1024_tick_offset(const CodeParams &p, size_t batch) { return (gather_order_bytes(p, batch) + 255) / 256 * 256; }
 size_t n1024_scratch_bytes(const CodeParams &p, size_t batch) { return n1024_tick_offset(p, batch) + 256; }
 
+static_assert(size_t(COLS) == kN1024xMinCols, "choose_reconstruct: at least one whole tile");
+
 hipError_t launch_reconstruct_n1024x(const CodeParams &p, const DevTables &t,
                                      const uint8_t *d_shards, size_t slen, size_t sstride,
                                      const uint8_t *d_present, const uint16_t *d_err_log,

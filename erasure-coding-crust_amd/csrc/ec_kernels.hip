@@ -575,25 +575,63 @@ size_t encode_scratch_bytes(const CodeParams &p, size_t plen, size_t batch) {
   return tiles * grid_y(batch) * 2 * size_t(p.k) * sizeof(uint2);
 }
 
+const char *kernel_name(Kernel k) {
+  switch (k) {
+#define ECAMD_NAME(X) \
+  case Kernel::X: return #X;
+    ECAMD_NAME(encode_k256w) ECAMD_NAME(encode_k256_packed) ECAMD_NAME(encode_kw)
+    ECAMD_NAME(encode_k512w) ECAMD_NAME(encode_k1024) ECAMD_NAME(encode_g)
+    ECAMD_NAME(reconstruct_n1024x) ECAMD_NAME(reconstruct_n1024) ECAMD_NAME(reconstruct_n1024_packed)
+    ECAMD_NAME(reconstruct_n4096) ECAMD_NAME(reconstruct_gen) ECAMD_NAME(reconstruct_g)
+#undef ECAMD_NAME
+    case Kernel::invalid: break;
+  }
+  return nullptr;
+}
+
+// The fast kernels read payload rows with 16-B loads and write shard rows with
+// 8-B stores (a single payload's pitch is never applied).  k = 256 has a
+// packed form for what they cannot take: payloads under one tile of pieces,
+// any payload base and pitch, any even shard base and pitch, while its
+// flattened piece space (pieces rounded up to 8, per payload) stays below
+// 2^32; past that, or with an odd shard base or pitch, the shape goes on to
+// the kernels below.
+Kernel choose_encode(const CodeParams &p, size_t plen, size_t pstride, size_t batch,
+                     uintptr_t payloads, uintptr_t shards, size_t sstride) {
+  if (batch == 0 || plen == 0) return Kernel::invalid;
+  const bool aligned = payloads % 16 == 0 && shards % 8 == 0 && (batch == 1 || pstride % 16 == 0) &&
+                       sstride % 8 == 0;
+  if (k256_applicable(p)) {
+    const size_t npp = (plen + 2 * 256 - 1) / (2 * 256);  // pieces per payload
+    if (aligned && npp >= kK256Tile) return p.n == 1024 ? Kernel::encode_k256w : Kernel::encode_kw;
+    const size_t npp8 = (npp + 7) / 8 * 8;  // (>= npp: also bounds the exactly flattened space of PK = 2)
+    if (shards % 2 == 0 && sstride % 2 == 0 && npp8 * batch + kK256Tile < (size_t(1) << 32))
+      return Kernel::encode_k256_packed;
+  }
+  if (aligned && k512w_applicable(p)) return Kernel::encode_k512w;
+  if (aligned && kw_applicable(p)) return Kernel::encode_kw;
+  if (aligned && k1024_applicable(p)) return Kernel::encode_k1024;
+  return Kernel::encode_g;
+}
+
 hipError_t launch_encode(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,
                          size_t plen, size_t pstride, size_t batch, uint8_t *d_shards,
                          size_t sstride, void *scratch, hipStream_t s, HostSig *sig) {
-  if (batch == 0 || plen == 0) return hipSuccess;
-  const bool aligned = (reinterpret_cast<uintptr_t>(d_payloads) % 16 == 0) &&
-                       (reinterpret_cast<uintptr_t>(d_shards) % 8 == 0) &&
-                       (batch == 1 || pstride % 16 == 0) && sstride % 8 == 0;
-  if (k256_applicable(p) &&
-      (k256_packed(plen, pstride, batch, reinterpret_cast<uintptr_t>(d_payloads),
-                   reinterpret_cast<uintptr_t>(d_shards), sstride)
-           ? k256_packed_ok(plen, batch, reinterpret_cast<uintptr_t>(d_shards), sstride)
-           : aligned))
-    return launch_encode_k256(p, t, d_payloads, plen, pstride, batch, d_shards, sstride, scratch, s);
-  if (aligned && k512w_applicable(p))
-    return launch_encode_k512w(p, t, d_payloads, plen, pstride, batch, d_shards, sstride, scratch, s);
-  if (aligned && kw_applicable(p))
-    return launch_encode_kw(p, t, d_payloads, plen, pstride, batch, d_shards, sstride, scratch, s);
-  if (aligned && k1024_applicable(p))
-    return launch_encode_k1024(p, t, d_payloads, plen, pstride, batch, d_shards, sstride, scratch, s);
+  switch (choose_encode(p, plen, pstride, batch, reinterpret_cast<uintptr_t>(d_payloads),
+                        reinterpret_cast<uintptr_t>(d_shards), sstride)) {
+    case Kernel::encode_k256w:
+      return launch_encode_k256w(p, t, d_payloads, plen, pstride, batch, d_shards, sstride, scratch, s);
+    case Kernel::encode_k256_packed:
+      return launch_encode_k256(p, t, d_payloads, plen, pstride, batch, d_shards, sstride, s);
+    case Kernel::encode_kw:
+      return launch_encode_kw(p, t, d_payloads, plen, pstride, batch, d_shards, sstride, scratch, s);
+    case Kernel::encode_k512w:
+      return launch_encode_k512w(p, t, d_payloads, plen, pstride, batch, d_shards, sstride, scratch, s);
+    case Kernel::encode_k1024:
+      return launch_encode_k1024(p, t, d_payloads, plen, pstride, batch, d_shards, sstride, scratch, s);
+    case Kernel::encode_g: break;
+    default: return hipSuccess;  // an empty call
+  }
   const size_t sl = shard_len(p.k, plen);
   const int G = groups_for(p.k);
   const size_t tiles = (sl / 2 + 4 * G - 1) / (4 * G);
@@ -689,39 +727,77 @@ size_t reconstruct_scratch_bytes(const CodeParams &p, size_t slen, size_t batch)
   return tiles * grid_y(batch) * 2 * size_t(p.n) * sizeof(uint2);
 }
 
+const ReconOverrides &recon_overrides() {
+  static const ReconOverrides o = [] {
+    const char *w = std::getenv("ECCR_AMD_RECON_WAVES"), *k = std::getenv("ECCR_AMD_RECON_PACKED");
+    ReconOverrides r;
+    r.waves8 = w && w[0] == '8';
+    r.force_packed = k && k[0] == '1';
+    return r;
+  }();
+  return o;
+}
+
+// The fast kernels read shard rows with 16-B loads.  The n = 1024 kernels
+// write out rows with 8-B stores and read a pattern's flag and locator rows
+// with vector loads (out8); reconstruct_n4096 and reconstruct_gen write with
+// 16-B stores (out16) and read those rows element-wise.  n = 1024 has a packed
+// form for payloads under one tile of columns and for any even shard base and
+// pitch, while its flattened column space (columns rounded up to 4, per
+// payload) stays below 2^32: past that it launches nothing.
+Kernel choose_reconstruct(const CodeParams &p, size_t slen, size_t sstride, size_t batch,
+                          uintptr_t shards, uintptr_t present, uintptr_t err_log, uintptr_t out,
+                          size_t ostride, bool waves8, bool force_packed) {
+  if (batch == 0 || slen < 2) return Kernel::invalid;
+  const bool aligned = shards % 16 == 0 && out % 8 == 0 && sstride % 16 == 0 &&
+                       (batch == 1 || ostride % 8 == 0);
+  const bool out8 = out % 8 == 0 && (batch == 1 || ostride % 8 == 0) && present % 16 == 0 &&
+                    err_log % 16 == 0;
+  const bool out16 = out % 16 == 0 && (batch == 1 || ostride % 16 == 0);
+  const size_t ncols = slen / 2;
+  if (n1024_applicable(p)) {
+    const bool packed = ncols < kN1024Cols || shards % 16 != 0 || sstride % 16 != 0;
+    if (!packed && aligned && out8 && !waves8 && ncols >= kN1024xMinCols) return Kernel::reconstruct_n1024x;
+    if (packed ? out8 && shards % 2 == 0 && sstride % 2 == 0 : aligned && out8) {
+      if (!packed && !force_packed) return Kernel::reconstruct_n1024;
+      const size_t ncols4 = (ncols + 3) / 4 * 4;
+      return ncols4 * batch + kN1024Cols < (size_t(1) << 32) ? Kernel::reconstruct_n1024_packed
+                                                             : Kernel::invalid;
+    }
+  }
+  if (aligned && out16 && n4096_applicable(p)) return Kernel::reconstruct_n4096;
+  if (aligned && out16 && decgen_applicable(p)) return Kernel::reconstruct_gen;
+  return Kernel::reconstruct_g;
+}
+
 hipError_t launch_reconstruct(const CodeParams &p, const DevTables &t, const uint8_t *d_shards,
                               size_t slen, size_t sstride, const uint8_t *d_present,
                               const uint16_t *d_err_log, const uint32_t *d_pattern, size_t batch,
                               uint8_t *d_out, size_t ostride, void *scratch, hipStream_t s) {
-  if (batch == 0 || slen < 2) return hipSuccess;
-  const bool aligned = (reinterpret_cast<uintptr_t>(d_shards) % 16 == 0) &&
-                       (reinterpret_cast<uintptr_t>(d_out) % 8 == 0) && sstride % 16 == 0 &&
-                       (batch == 1 || ostride % 8 == 0);
-  const bool out8 = reinterpret_cast<uintptr_t>(d_out) % 8 == 0 && (batch == 1 || ostride % 8 == 0) &&
-                    reinterpret_cast<uintptr_t>(d_present) % 16 == 0 &&
-                    reinterpret_cast<uintptr_t>(d_err_log) % 16 == 0;  // vector loads of flag / E rows
-  // ECCR_AMD_RECON_WAVES=8 (experiments): the 8-wave kernel where the 12-wave one applies
-  static const bool waves8 = [] {
-    const char *e = std::getenv("ECCR_AMD_RECON_WAVES");
-    return e && e[0] == '8';
-  }();
-  const bool packed1024 = n1024_packed(slen, reinterpret_cast<uintptr_t>(d_shards), sstride);
-  if (n1024_applicable(p) && !packed1024 && aligned && out8 && !waves8 && slen / 2 >= 48)
-    return launch_reconstruct_n1024x(p, t, d_shards, slen, sstride, d_present, d_err_log, d_pattern, batch,
-                                     d_out, ostride, scratch, s);
-  if (n1024_applicable(p) &&
-      (packed1024 ? out8 && reinterpret_cast<uintptr_t>(d_shards) % 2 == 0 && sstride % 2 == 0
-                  : aligned && out8))
-    return launch_reconstruct_n1024(p, t, d_shards, slen, sstride, d_present, d_err_log, d_pattern, batch,
-                                    d_out, ostride, scratch, s);
-  if (aligned && n4096_applicable(p) && reinterpret_cast<uintptr_t>(d_out) % 16 == 0 &&
-      (batch == 1 || ostride % 16 == 0))
-    return launch_reconstruct_n4096(p, t, d_shards, slen, sstride, d_present, d_err_log, d_pattern, batch,
-                                    d_out, ostride, scratch, s);
-  if (aligned && decgen_applicable(p) && reinterpret_cast<uintptr_t>(d_out) % 16 == 0 &&
-      (batch == 1 || ostride % 16 == 0))
-    return launch_reconstruct_gen(p, t, d_shards, slen, sstride, d_present, d_err_log, d_pattern, batch,
-                                  d_out, ostride, scratch, s);
+  const ReconOverrides &o = recon_overrides();
+  const Kernel kern = choose_reconstruct(
+      p, slen, sstride, batch, reinterpret_cast<uintptr_t>(d_shards),
+      reinterpret_cast<uintptr_t>(d_present), reinterpret_cast<uintptr_t>(d_err_log),
+      reinterpret_cast<uintptr_t>(d_out), ostride, o.waves8, o.force_packed);
+  switch (kern) {
+    case Kernel::reconstruct_n1024x:
+      return launch_reconstruct_n1024x(p, t, d_shards, slen, sstride, d_present, d_err_log, d_pattern,
+                                       batch, d_out, ostride, scratch, s);
+    case Kernel::reconstruct_n1024:
+    case Kernel::reconstruct_n1024_packed:
+      return launch_reconstruct_n1024(p, t, kern == Kernel::reconstruct_n1024_packed, d_shards, slen,
+                                      sstride, d_present, d_err_log, d_pattern, batch, d_out, ostride,
+                                      scratch, s);
+    case Kernel::reconstruct_n4096:
+      return launch_reconstruct_n4096(p, t, d_shards, slen, sstride, d_present, d_err_log, d_pattern,
+                                      batch, d_out, ostride, scratch, s);
+    case Kernel::reconstruct_gen:
+      return launch_reconstruct_gen(p, t, d_shards, slen, sstride, d_present, d_err_log, d_pattern,
+                                    batch, d_out, ostride, scratch, s);
+    case Kernel::reconstruct_g: break;
+    default:  // an empty call, or the packed form past its 2^32 flattened columns
+      return batch == 0 || slen < 2 ? hipSuccess : hipErrorInvalidValue;
+  }
   const int G = groups_for(p.n);
   const size_t tiles = (slen / 2 + 4 * G - 1) / (4 * G);
   const bool lds = p.n <= uint32_t(kLdsSlots);

@@ -104,6 +104,43 @@ size_t encode_scratch_bytes(const CodeParams &p, size_t payload_len, size_t batc
 bool encode_scratch_optional(const CodeParams &p);  // only a tile counter: static schedule without it
 size_t reconstruct_scratch_bytes(const CodeParams &p, size_t shard_len, size_t batch);
 
+// The kernel a batch call runs: decided by the code, the lengths, the batch
+// and the alignment of every base and pitch, in choose_encode /
+// choose_reconstruct and nowhere else (launch_encode / launch_reconstruct
+// switch on the result).  `invalid`: nothing is launched (an empty call, or a
+// packed form whose flattened space passes 2^32: hipErrorInvalidValue).
+enum class Kernel {
+  invalid,
+  encode_k256w,
+  encode_k256_packed,  // encode_k256<1024, 2> / encode_k256<2048, 1>
+  encode_kw,
+  encode_k512w,
+  encode_k1024,
+  encode_g,
+  reconstruct_n1024x,
+  reconstruct_n1024,         // reconstruct_n1024<false>
+  reconstruct_n1024_packed,  // reconstruct_n1024<true>
+  reconstruct_n4096,
+  reconstruct_gen,
+  reconstruct_g,
+};
+const char *kernel_name(Kernel k);  // the enumerator's name; nullptr for invalid
+
+// Pure host functions: the pointers are only looked at as addresses, no device
+// is needed.  recon_overrides(): the experiment switches ECCR_AMD_RECON_WAVES=8
+// (waves8: the 8-wave kernel where the 12-wave one applies) and
+// ECCR_AMD_RECON_PACKED=1 (force_packed: reconstruct_n1024 packed at every
+// size), read from the environment once per process.
+Kernel choose_encode(const CodeParams &p, size_t payload_len, size_t payload_stride, size_t batch,
+                     uintptr_t payloads, uintptr_t shards, size_t shard_stride);
+struct ReconOverrides {
+  bool waves8 = false, force_packed = false;
+};
+const ReconOverrides &recon_overrides();
+Kernel choose_reconstruct(const CodeParams &p, size_t shard_len, size_t shard_stride, size_t batch,
+                          uintptr_t shards, uintptr_t present, uintptr_t err_log, uintptr_t out,
+                          size_t out_stride, bool waves8, bool force_packed);
+
 hipError_t launch_encode(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,
                          size_t payload_len, size_t payload_stride, size_t batch, uint8_t *d_shards,
                          size_t shard_stride, void *scratch, hipStream_t s, HostSig *sig = nullptr);
@@ -162,18 +199,18 @@ hipError_t warm_encode_tiny(hipStream_t s);  // device set-up: the first launche
 
 // specialised kernels (enc_k256.hip)
 bool k256_applicable(const CodeParams &p);
-// reconstruct_n1024 runs packed (flattened columns, any even shard pitch)
-bool n1024_packed(size_t slen, uintptr_t sh, size_t sstride);
-// the packed (flattened-piece, any-alignment) encode_k256 applies: small
-// payloads or pitches the unpacked kernel cannot take; ..._ok: its own limits
-bool k256_packed(size_t plen, size_t pstride, size_t batch, uintptr_t pay, uintptr_t sh, size_t sstride);
-bool k256_packed_ok(size_t plen, size_t batch, uintptr_t sh, size_t sstride);
-// scratch: k256_scratch_bytes (the n = 1024 unpacked form's tile counter)
+// tile sizes the choosers test (static_asserts beside the kernels): pieces per
+// tile of the unpacked k = 256 encodes' dispatch, columns per tile of
+// reconstruct_n1024<false>, and the fewest columns reconstruct_n1024x takes
+constexpr size_t kK256Tile = 128, kN1024Cols = 32, kN1024xMinCols = 48;
+// encode_k256_packed (choose_encode): the packed (flattened-piece,
+// any-alignment) kernel for small payloads or pitches the unpacked kernels
+// cannot take; no scratch
 hipError_t launch_encode_k256(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,
                               size_t plen, size_t pstride, size_t batch, uint8_t *d_shards,
-                              size_t sstride, void *scratch, hipStream_t s);
+                              size_t sstride, hipStream_t s);
 size_t k256_scratch_bytes(const CodeParams &p);
-// the n = 1024, unpacked case of launch_encode_k256: two 8-wave workgroups per
+// encode_k256w (n = 1024, unpacked): two 8-wave workgroups per
 // CU on the compact image, tiles scheduled dynamically from a counter in
 // `scratch` (enc_k256w.hip)
 hipError_t launch_encode_k256w(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,
@@ -216,7 +253,8 @@ hipError_t launch_gather_order(const CodeParams &p, const uint8_t *d_present,
 
 // specialised kernels (dec_n1024.hip); scratch: n1024_scratch_bytes(p, batch)
 bool n1024_applicable(const CodeParams &p);
-hipError_t launch_reconstruct_n1024(const CodeParams &p, const DevTables &t,
+// packed (choose_reconstruct): flattened columns, any even shard pitch and base
+hipError_t launch_reconstruct_n1024(const CodeParams &p, const DevTables &t, bool packed,
                                     const uint8_t *d_shards, size_t slen, size_t sstride,
                                     const uint8_t *d_present, const uint16_t *d_err_log,
                                     const uint32_t *d_pattern, size_t batch, uint8_t *d_out,

@@ -275,44 +275,14 @@ __device__ __forceinline__ void store_chunk_any(uint8_t *dst, const uint4 val, u
 // piece0 + 8c of the tile's payload (SH), or, packed, pieces [pc, pc + 8) of
 // the payload bc that owns flattened slot tile * TILE + 8c (computed here, not
 // kept live across the FFTs)
-// The common case of store_own, decided once (uniform): 16-B aligned rows, the
-// whole tile inside the payload and all 256 rows below n_validators -- one
-// aligned 16-B streaming store per lane and row, addresses stepped, no
-// per-lane tests (the general form made the compiler merge its two store
-// shapes into a 4-B + a misaligned 12-B store per chunk)
-__device__ __forceinline__ bool rows_fast_ok(const uint8_t *SH, uint64_t sstride, uint32_t s0, int nv,
-                                             uint64_t piece0, uint64_t npieces) {
-  return ((sstride | reinterpret_cast<uintptr_t>(SH)) & 15) == 0 && piece0 + TILE <= npieces &&
-         int(s0) + 256 <= nv;
-}
-__device__ __forceinline__ void store_rows_fast(const uint8_t *xbase, uint8_t *SH, uint64_t sstride,
-                                                uint32_t s0, uint64_t piece0, uint32_t wave, uint32_t lane) {
-  typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-  const uint32_t c = lane & 15;
-  const uint32_t v0 = wave * 4 + (lane >> 4);
-  const uint32_t sa = lds_addr(xbase + c * XCH_BYTES) + soff(v0, c);
-  uint8_t *dst = SH + uint64_t(s0 + v0) * sstride + 2 * (piece0 + 8 * c);
-  const uint64_t dstep = uint64_t(4 * WAVES) * sstride;
-#pragma unroll
-  for (int it = 0; it < 256 / (4 * WAVES); ++it) {  // soff is GF(2)-linear in v = it * 4 WAVES | v0
-    const v4u val = *(const __attribute__((address_space(3))) v4u *)(uintptr_t(sa ^ soff(uint32_t(it) * 4 * WAVES, 0)));
-    // streaming (non-temporal): rows are written once, not re-read
-    __builtin_nontemporal_store(val, reinterpret_cast<v4u *>(dst + it * dstep));
-  }
-}
-
+// (The unpacked form, PACKED = false, is not instantiated any more: its shapes
+// run encode_k256w and encode_kw<8>.)
 template <bool PACKED>
 __device__ __forceinline__ void store_own(const uint8_t *xbase, uint8_t *SH, uint64_t sstride,
                                           uint32_t s0, int nv, uint64_t piece0, uint64_t npieces,
                                           uint32_t wave, uint32_t lane, uint64_t tile, uint32_t npp8,
                                           uint32_t batch) {
   asm volatile("" : "+v"(lane));  // recomputed here, not kept live across the FFTs
-  if constexpr (!PACKED) {
-    if (rows_fast_ok(SH, sstride, s0, nv, piece0, npieces)) {
-      store_rows_fast(xbase, SH, sstride, s0, piece0, wave, lane);
-      return;
-    }
-  }
   const uint32_t c = lane & 15;
   uint64_t p = piece0 + 8 * c;
   if constexpr (PACKED) {
@@ -636,54 +606,31 @@ __global__ void __launch_bounds__(THREADS) encode_k256(const uint8_t *__restrict
 
 bool k256_applicable(const CodeParams &p) { return p.k == 256 && (p.n == 1024 || p.n == 2048); }
 
-// packed tiles: pieces per payload below one tile, or pitches / bases the
-// unpacked kernel's 16-B loads and 8-B stores cannot take (any even shard
-// pitch and shard base, any payload pitch and base)
-bool k256_packed(size_t plen, size_t pstride, size_t batch, uintptr_t pay, uintptr_t sh, size_t sstride) {
-  const size_t npp = (plen + 2 * K - 1) / (2 * K);
-  const bool aligned = pay % 16 == 0 && sh % 8 == 0 && (batch == 1 || pstride % 16 == 0) && sstride % 8 == 0;
-  return !aligned || npp < size_t(TILE);
-}
-
-bool k256_packed_ok(size_t plen, size_t batch, uintptr_t sh, size_t sstride) {
-  const size_t npp8 = ((plen + 2 * K - 1) / (2 * K) + 7) / 8 * 8;
-  return sh % 2 == 0 && sstride % 2 == 0 && npp8 * batch + TILE < (size_t(1) << 32);
-}  // (npp8 >= npp: also bounds the exactly flattened piece space of PK = 2)
+static_assert(size_t(TILE) == kK256Tile, "choose_encode tests this tile");
 
 size_t k256_scratch_bytes(const CodeParams &) { return 256; }  // the unpacked kernels' tile counter
 
+// the packed kernel, PK = 2 at n = 1024 and PK = 1 at n = 2048 (the unpacked
+// shapes run encode_k256w and encode_kw<8>); choose_encode has checked the
+// even shard base and pitch and the 2^32 bound of the flattened piece space
 hipError_t launch_encode_k256(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,
                               size_t plen, size_t pstride, size_t batch, uint8_t *d_shards,
-                              size_t sstride, void *scratch, hipStream_t s) {
+                              size_t sstride, hipStream_t s) {
   int cus = 0;
-  const bool packed = k256_packed(plen, pstride, batch, reinterpret_cast<uintptr_t>(d_payloads),
-                                  reinterpret_cast<uintptr_t>(d_shards), sstride);
-  if (p.n == 1024 && !packed)
-    return launch_encode_k256w(p, t, d_payloads, plen, pstride, batch, d_shards, sstride, scratch, s);
-  if (p.n == 2048 && !packed)  // round 6: the two-workgroups-per-CU model (enc_kw.hip)
-    return launch_encode_kw(p, t, d_payloads, plen, pstride, batch, d_shards, sstride, scratch, s);
-  if (packed && !k256_packed_ok(plen, batch, reinterpret_cast<uintptr_t>(d_shards), sstride))
-    return hipErrorInvalidValue;
   const void *fn = p.n == 1024 ? reinterpret_cast<const void *>(&encode_k256<1024, 2>)
-                               : (packed ? reinterpret_cast<const void *>(&encode_k256<2048, 1>)
-                                         : reinterpret_cast<const void *>(&encode_k256<2048, 0>));
+                               : reinterpret_cast<const void *>(&encode_k256<2048, 1>);
   if (const hipError_t e = prepare_kernel(fn, LDS_BYTES, &cus); e != hipSuccess) return e;
   const size_t sl = shard_len(p.k, plen);
   const size_t npp8 = (sl / 2 + 7) / 8 * 8;
-  const size_t tiles = !packed       ? (sl / 2 + TILE - 1) / TILE * batch
-                       : p.n == 1024 ? ((sl / 2) * batch + 7) / 8  // wave tasks, spread over the CUs
-                                     : (npp8 * batch + TILE - 1) / TILE;
+  const size_t tiles = p.n == 1024 ? ((sl / 2) * batch + 7) / 8  // wave tasks, spread over the CUs
+                                   : (npp8 * batch + TILE - 1) / TILE;
   const unsigned grid = unsigned(tiles < size_t(cus) ? tiles : size_t(cus));
 #define ECAMD_K256(NN, PK)                                                                       \
   hipLaunchKernelGGL((encode_k256<NN, PK>), dim3(grid), dim3(THREADS), LDS_BYTES, s, d_payloads,   \
                      uint64_t(plen), uint64_t(pstride), d_shards, uint64_t(sl), uint64_t(sstride), \
                      int(p.nv), uint32_t(batch), uint32_t(npp8), t)
-  if (p.n == 1024) {
-    ECAMD_K256(1024, 2);  // (packed: the unpacked n = 1024 case is encode_k256w)
-  } else {
-    if (packed) ECAMD_K256(2048, 1);
-    else ECAMD_K256(2048, 0);
-  }
+  if (p.n == 1024) ECAMD_K256(1024, 2);
+  else ECAMD_K256(2048, 1);
 #undef ECAMD_K256
   return hipGetLastError();
 }

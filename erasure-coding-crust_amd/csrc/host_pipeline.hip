@@ -195,14 +195,21 @@ NPRSResult ECCR_AMD_encode_host_batch(unsigned long nv, const uint8_t *h_payload
   Pipeline *pl = d ? pipeline() : nullptr;
   if (!pl) return res(NPRS_RESULT_UNKNOWN_CODE_PARAM);
   if (chunk == 0) chunk = auto_chunk(plen + size_t(nv) * sl, batch);
-  // Device rows use the host stride (one linear copy) when it already suits the
-  // fast kernels or rows are short: a 2-D copy of many narrow rows is
+  // Device rows use the host stride (one linear copy up) when it already suits
+  // the fast kernels or rows are short: a 2-D copy of many narrow rows is
   // descriptor-bound (2-byte rows ran at ~10 us per row).  Otherwise rows are
   // re-pitched to aligned device strides by a 2-D copy of long rows.
   const bool pay_lin = pstride % 16 == 0 || plen < 256;
   const bool sh_lin = sstride % 8 == 0 || sl < 256;
   const size_t dps = pay_lin ? pstride : round16(plen);
   const size_t dss = sh_lin ? sstride : (sl + 63) / 64 * 64;
+  // The rows come back in one linear copy only if that writes nothing but the
+  // rows: tight rows, or short padded rows whose span was first brought up
+  // from the caller's buffer, so that the bytes between the rows come back as
+  // they were (the kernels write shard_len bytes per row).  Long padded rows
+  // come back by a 2-D copy.
+  const bool sh_pre = sh_lin && sstride != sl && sl < 256;
+  const bool sh_down_lin = sh_lin && (sstride == sl || sh_pre);
   for (unsigned long c0 = 0, i = 0; c0 < batch; c0 += chunk, ++i) {
     Slot &s = pl->slot[i % kSlots];
     const size_t cb = batch - c0 < chunk ? batch - c0 : chunk;
@@ -217,14 +224,16 @@ NPRSResult ECCR_AMD_encode_host_batch(unsigned long nv, const uint8_t *h_payload
         pay_lin ? hipMemcpyAsync(s.d_a, hp, (cb - 1) * pstride + plen, hipMemcpyHostToDevice, s.stream)
                 : hipMemcpy2DAsync(s.d_a, dps, hp, pstride, plen, cb, hipMemcpyHostToDevice, s.stream);
     if (!ok(up, "H2D payloads") ||
+        (sh_pre && !ok(hipMemcpyAsync(s.d_b, hs, (cb * nv - 1) * sstride + sl, hipMemcpyHostToDevice, s.stream),
+                       "H2D shard rows' surroundings")) ||
         !ok(launch_encode(p, device_tables(d), s.d_a, plen, dps, cb, s.d_b, dss, scratch, s.stream),
             "encode launch"))
       return res(NPRS_RESULT_UNKNOWN_CODE_PARAM);
     const hipError_t down =
-        sh_lin ? hipMemcpyAsync(hs, s.d_b, (cb * nv - 1) * sstride + sl, hipMemcpyDeviceToHost,
-                                s.stream)
-               : hipMemcpy2DAsync(hs, sstride, s.d_b, dss, sl, cb * nv, hipMemcpyDeviceToHost,
-                                  s.stream);
+        sh_down_lin ? hipMemcpyAsync(hs, s.d_b, (cb * nv - 1) * sstride + sl, hipMemcpyDeviceToHost,
+                                     s.stream)
+                    : hipMemcpy2DAsync(hs, sstride, s.d_b, dss, sl, cb * nv, hipMemcpyDeviceToHost,
+                                       s.stream);
     if (!ok(down, "D2H shards"))
       return res(NPRS_RESULT_UNKNOWN_CODE_PARAM);
   }
@@ -281,8 +290,11 @@ NPRSResult ECCR_AMD_reconstruct_host_batch(unsigned long nv, const uint8_t *h_sh
   if (!pl) return res(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
   if (chunk == 0) chunk = auto_chunk(size_t(cnt) * sstride + size_t(slen) * p.k, batch);
   const size_t dss = (slen + 63) / 64 * 64, ob = slen * p.k;
-  const bool out_lin = ostride % 8 == 0 || ob < 256;  // as in encode: linear copy if it suits
+  const bool out_lin = ostride % 8 == 0 || ob < 256;  // as in encode: the host pitch if it suits
   const size_t dos = out_lin ? ostride : ob;
+  // as in encode: a linear copy back only where it writes nothing but the rows
+  const bool out_pre = out_lin && ostride != ob && ob < 256;
+  const bool out_down_lin = out_lin && (ostride == ob || out_pre);
   for (unsigned long c0 = 0, i = 0; c0 < batch; c0 += chunk, ++i) {
     Slot &s = pl->slot[i % kSlots];
     const size_t cb = batch - c0 < chunk ? batch - c0 : chunk;
@@ -352,7 +364,10 @@ NPRSResult ECCR_AMD_reconstruct_host_batch(unsigned long nv, const uint8_t *h_sh
         ok(hipMemcpyAsync(s.d_meta, s.h_meta, rows_at + size_t(npat) * p.n, hipMemcpyHostToDevice,
                           s.stream),
            "H2D patterns") &&
-        ok(hipEventRecord(s.staged, s.stream), "staging event");
+        ok(hipEventRecord(s.staged, s.stream), "staging event") &&
+        (!out_pre || ok(hipMemcpyAsync(s.d_c, h_out + c0 * ostride, (cb - 1) * ostride + ob,
+                                       hipMemcpyHostToDevice, s.stream),
+                        "H2D out rows' surroundings"));
     if (good) {
       hipLaunchKernelGGL(scatter_present, dim3(unsigned(cnt), unsigned(cb < 65535 ? cb : 65535)), dim3(256),
                          0, s.stream, s.d_a, uint64_t(sstride), d_idx, uint32_t(cnt), uint64_t(slen),
@@ -364,10 +379,11 @@ NPRSResult ECCR_AMD_reconstruct_host_batch(unsigned long nv, const uint8_t *h_sh
              ok(launch_reconstruct(p, device_tables(d), s.d_b, slen, dss, d_present, s.d_elog,
                                    d_pat, cb, s.d_c, dos, scratch, s.stream),
                 "reconstruct launch") &&
-             ok(out_lin ? hipMemcpyAsync(h_out + c0 * ostride, s.d_c, (cb - 1) * ostride + ob,
-                                         hipMemcpyDeviceToHost, s.stream)
-                        : hipMemcpy2DAsync(h_out + c0 * ostride, ostride, s.d_c, ob, ob, cb,
-                                           hipMemcpyDeviceToHost, s.stream),
+             ok(out_down_lin
+                    ? hipMemcpyAsync(h_out + c0 * ostride, s.d_c, (cb - 1) * ostride + ob, hipMemcpyDeviceToHost,
+                                     s.stream)
+                    : hipMemcpy2DAsync(h_out + c0 * ostride, ostride, s.d_c, dos, ob, cb,
+                                       hipMemcpyDeviceToHost, s.stream),
                 "D2H payloads");
     }
     if (!good) return res(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);

@@ -121,6 +121,8 @@ def lib():
             "ECCR_AMD_error_locator_patterns": (NPRSResult, [ul, vp, vp, ul, vp, vp]),
             "ECCR_AMD_reconstruct_batch_patterns": (NPRSResult, [ul, vp, ul, ul, vp, vp, vp, ul, vp,
                                                                  ul, vp]),
+            "ECCR_AMD_encode_kernel": (C.c_char_p, [ul, vp, ul, ul, ul, vp, ul]),
+            "ECCR_AMD_reconstruct_kernel": (C.c_char_p, [ul, vp, ul, ul, vp, vp, ul, vp, ul]),
             "ECCR_AMD_locator_cache_stats": (NPRSResult, [up, up]),
             "ECCR_AMD_encode_workspace_bytes": (ul, [ul, ul, ul]),
             "ECCR_AMD_error_locator_workspace_bytes": (ul, [ul, ul]),
@@ -360,6 +362,23 @@ def reconstruct_batch_ws(nv, d_shards, shard_len_, shard_stride, d_present, d_er
         nv, _p(d_shards), shard_len_, shard_stride, _p(d_present), _p(d_err_log),
         None if d_pattern is None else _p(d_pattern), batch, _p(d_out), out_stride, wp, wb,
         _stream(stream)), "reconstruct_batch_ws")
+
+
+def encode_kernel(nv, d_payloads, payload_len, payload_stride, batch, d_shards, shard_stride):
+    """Name of the kernel encode_batch would launch for these arguments, or None (diagnostic;
+    host-only: tensors, arrays or plain integer addresses)."""
+    r = lib().ECCR_AMD_encode_kernel(nv, _p(d_payloads), payload_len, payload_stride, batch,
+                                     _p(d_shards), shard_stride)
+    return None if r is None else r.decode()
+
+
+def reconstruct_kernel(nv, d_shards, shard_len_, shard_stride, d_present, d_err_log, batch, d_out,
+                       out_stride):
+    """Name of the kernel reconstruct_batch would launch for these arguments, or None."""
+    r = lib().ECCR_AMD_reconstruct_kernel(nv, _p(d_shards), shard_len_, shard_stride,
+                                          _p(d_present), _p(d_err_log), batch, _p(d_out),
+                                          out_stride)
+    return None if r is None else r.decode()
 
 
 def locator_cache_stats():

@@ -153,6 +153,29 @@ struct NPRSResult ECCR_AMD_reconstruct_batch_patterns(
     const uint32_t *d_pattern, unsigned long batch, uint8_t *d_out, unsigned long out_stride,
     void *stream);
 
+/* ---- diagnostics ---------------------------------------------------------
+ * The name of the kernel ECCR_AMD_encode_batch / ECCR_AMD_reconstruct_batch
+ * (and their _ws / _patterns forms) would launch in this process for exactly
+ * these arguments: the choice depends on the code, the lengths, the batch and
+ * on the alignment of every base and pitch.  A static string, one of
+ *   encode_k256w, encode_k256_packed, encode_kw, encode_k512w, encode_k1024,
+ *   encode_g, reconstruct_n1024x, reconstruct_n1024, reconstruct_n1024_packed,
+ *   reconstruct_n4096, reconstruct_gen, reconstruct_g,
+ * or NULL where the call would launch nothing (invalid parameters, an empty
+ * batch).  Host-only: no pointer is dereferenced and no device is needed, so
+ * made-up addresses may be passed.  For tests and performance triage (a
+ * misaligned buffer silently costs a slower kernel); not a stable part of the
+ * interface: the names follow the kernels. */
+const char *ECCR_AMD_encode_kernel(unsigned long n_validators, const uint8_t *d_payloads,
+                                   unsigned long payload_len, unsigned long payload_stride,
+                                   unsigned long batch, const uint8_t *d_shards,
+                                   unsigned long shard_stride);
+const char *ECCR_AMD_reconstruct_kernel(unsigned long n_validators, const uint8_t *d_shards,
+                                        unsigned long shard_len, unsigned long shard_stride,
+                                        const uint8_t *d_present, const uint16_t *d_err_log,
+                                        unsigned long batch, const uint8_t *d_out,
+                                        unsigned long out_stride);
+
 /* Hits / misses of the per-device locator cache of ECCR_reconstruct (the
  * locator of a pattern is computed once and reused while it is among the 64
  * most recent patterns). */

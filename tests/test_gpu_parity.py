@@ -193,7 +193,8 @@ def _batch_case(nv, plen, batch, cnt_key="threshold", seed0=0, pad=0):
     (46, 70001, 2, 64), (65, 9999, 3, 16), (129, 33333, 2, 16), (257, 100001, 2, 64),
     (512, 200001, 2, 64), (765, 300001, 2, 64), (600, 1, 2, 16),
     # n = 2048 / 4096 with k = 256 / 512: encode with per-coset table images
-    # (encode_k256<2048>, encode_k512w), reconstruct by halves / quarters
+    # (encode_kw<8>, its packed form encode_k256<2048, 1> for the 5000-byte
+    # payloads, encode_k512w), reconstruct by halves / quarters
     # with k < 1024 outputs
     (1025, 5000, 3, 64), (1500, 200001, 2, 64), (2048, 100001, 2, 16), (2500, 300001, 2, 64),
     (3069, 4097, 2, 16)])
