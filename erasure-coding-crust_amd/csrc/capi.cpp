@@ -681,6 +681,8 @@ const char *ECCR_AMD_reconstruct_kernel(unsigned long nv, const uint8_t *d_shard
       reinterpret_cast<uintptr_t>(d_out), ostride, o.waves8, o.force_packed));
 }
 
+int ECCR_AMD_reconstruct_n1024x_waves(unsigned long slen) { return n1024x_waves(slen); }
+
 NPRSResult ECCR_AMD_locator_cache_stats(unsigned long *hits, unsigned long *misses) {
   DeviceState *d = device_state();
   if (!d) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);

@@ -1,8 +1,10 @@
 // dec_n1024x.hip — reconstruct for n = 1024, k = 256 (n_validators 766..1024,
-// the BASELINE headline) with 12 waves per CU: three per SIMD instead of the
-// two of reconstruct_n1024 (dec_n1024.hip), for the latency the 2-wave form
-// leaves exposed (31% of wave time waiting to issue, the
-// VALU ~57% busy at 2 waves per SIMD).
+// the BASELINE headline) with 12 or 16 waves per CU: three or four per SIMD
+// instead of the two of reconstruct_n1024 (dec_n1024.hip), for the latency
+// the 2-wave form leaves exposed (31% of wave time waiting
+// to issue, the VALU ~57% busy at 2 waves per SIMD).  One kernel template,
+// reconstruct_n1024x<WAVES>; the 12-wave form first, what the 16-wave form
+// changes at the end of this comment.
 //
 // The per-wave work is reconstruct_n1024's (one byte-planar group of 4 shard
 // columns per wave; gather + E[v] scaling, IFFT_1024 in radix-16 register
@@ -23,6 +25,17 @@
 //    not before the transform.
 // Tile = 48 shard columns (12 waves x 4); 1 MB at n_validators 1024 is 1954
 // columns, 41 tiles per payload.
+//
+// 16 waves (shards of kN1024x16MinCols columns and more; n1024x_waves):
+//  * LDS = the 32 KB image + 16 x 8 KB regions = 160 KB, all a workgroup may
+//    take: no staging area.  Phase 5's received rows are read from the shards
+//    again (L2: the gather read the same lines earlier in the tile), 8 B per
+//    lane and row, requested beside the E[y] tables after IFFT pass C.  The
+//    schedule word sits in dword 1 of the image's first kCImgSub1 entry, which
+//    no table fetch reads (ctab: dword 0 of those entries only).
+//  * <= 128 VGPRs (launch bounds 1024).
+//  * Tile = 64 columns: a row segment is 128 B, one gather slot per thread
+//    (1024 threads, 1024 slots); 1 MB at n_validators 1024 is 31 tiles.
 #include <hip/hip_runtime.h>
 
 #include "dec_n1024_common.hpp"
@@ -33,21 +46,32 @@
 namespace ecamd {
 namespace {
 using namespace n1024;
-constexpr int WAVES = 12;
-constexpr int THREADS = 64 * WAVES;
-constexpr int COLS = 4 * WAVES;  // shard columns per tile
 constexpr int TAB_REGION = int(kCImgBytes);  // the element-indexed compact image
 static_assert(TAB_REGION % 8192 == 0, "regions 8 KB aligned: region addresses are base | rz");
-// the tile schedule's LDS word, after the regions
-// phase 5's received rows y < 256: row slot (y & 3) << 6 | y >> 2 at a 112-B
-// pitch, so that its reads (y = 4 lane + q) are at most 2-way
-constexpr uint32_t STG = uint32_t(TAB_REGION + WAVES * REG_BYTES);
 constexpr uint32_t STG_PITCH = 112;
-__device__ __forceinline__ uint32_t stg_row(uint32_t y) { return STG + (((y & 3) << 6) | (y >> 2)) * STG_PITCH; }
-constexpr uint32_t SLOT = STG + 256 * STG_PITCH;
-constexpr int LDS_BYTES = int(SLOT + 16);
-static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
-constexpr int ROW_WORDS = COLS / 2;  // dwords of a row segment (96 B)
+// the two forms' sizes and LDS maps
+template <int WAVES>
+struct Form {
+  static_assert(WAVES == 12 || WAVES == 16, "three or four waves per SIMD");
+  static constexpr int THREADS = 64 * WAVES;
+  static constexpr int COLS = 4 * WAVES;     // shard columns per tile
+  static constexpr int ROW_WORDS = COLS / 2;  // dwords of a row segment (96 B / 128 B)
+  // gather slots per thread: tid and, with 768 threads, 768 + tid below 1024
+  static constexpr int SLOTS = (N + THREADS - 1) / THREADS;
+  // 12 waves: phase 5's received rows y < 256 staged after the regions, row
+  // slot (y & 3) << 6 | y >> 2 at a 112-B pitch, so that its reads
+  // (y = 4 lane + q) are at most 2-way; then the tile schedule's LDS word.
+  // 16 waves: nothing after the regions, the schedule word in the image
+  static constexpr bool STAGED = WAVES == 12;
+  static constexpr uint32_t STG = uint32_t(TAB_REGION + WAVES * REG_BYTES);
+  static constexpr uint32_t SLOT = STAGED ? STG + 256 * STG_PITCH : kCImgSub1 + 4;
+  static constexpr int LDS_BYTES = STAGED ? int(SLOT + 16) : int(STG);
+  static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
+};
+template <int WAVES>
+__device__ __forceinline__ uint32_t stg_row(uint32_t y) {
+  return Form<WAVES>::STG + (((y & 3) << 6) | (y >> 2)) * STG_PITCH;
+}
 
 // Region address of position v (8-byte cells, GF(2)-linear): conflict-free
 // for the reads (2 x 32 lanes) and writes (4 x 16 lanes) of the three layouts
@@ -185,10 +209,12 @@ __device__ __forceinline__ void ipassC2(S16 &s) {
   }
 }
 
-// bytes [0, avail) (avail < 96) of a 16-B aligned row slice into w[24], zero
-// beyond: whole dwords at immediate offsets under a uniform count, the last
-// one masked (an aligned dword holding a wanted byte never crosses a page)
-__device__ __forceinline__ void load_row_tail96(const uint8_t *row, uint32_t avail, uint32_t (&w)[ROW_WORDS]) {
+// bytes [0, avail) (avail < 4 ROW_WORDS) of a 16-B aligned row slice into
+// w[ROW_WORDS], zero beyond: whole dwords at immediate offsets under a uniform
+// count, the last one masked (an aligned dword holding a wanted byte never
+// crosses a page)
+template <int ROW_WORDS>
+__device__ __forceinline__ void load_row_tail(const uint8_t *row, uint32_t avail, uint32_t (&w)[ROW_WORDS]) {
   const uint32_t nw = (avail + 3) / 4;  // wave-uniform
   const uint32_t last = (avail & 3) ? (1u << (8 * (avail & 3))) - 1 : ~0u;
   const uint32_t *r = reinterpret_cast<const uint32_t *>(row);
@@ -201,11 +227,15 @@ __device__ __forceinline__ void load_row_tail96(const uint8_t *row, uint32_t ava
 
 }  // namespace
 
-__global__ void __launch_bounds__(THREADS) reconstruct_n1024x(
+template <int WAVES>
+__global__ void __launch_bounds__(64 * WAVES) reconstruct_n1024x(
     const uint8_t *__restrict__ shards, uint64_t slen, uint64_t sstride,
     const uint8_t *__restrict__ present, const uint16_t *__restrict__ elog,
     const uint32_t *__restrict__ pattern, const uint32_t *__restrict__ order,
     uint8_t *__restrict__ out, uint64_t ostride, int nv, uint32_t batch, uint32_t *tick, DevTables t) {
+  using F = Form<WAVES>;
+  constexpr int THREADS = F::THREADS, COLS = F::COLS, ROW_WORDS = F::ROW_WORDS;
+  constexpr uint32_t SLOT = F::SLOT;
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   uint8_t *regions = lds + TAB_REGION;
   // Tiles are handed out dynamically: a workgroup's first tile is blockIdx.x,
@@ -244,14 +274,14 @@ __global__ void __launch_bounds__(THREADS) reconstruct_n1024x(
   const uint64_t total = uint64_t(tiles_pp) * batch;
   const uint32_t wave_s = __builtin_amdgcn_readfirstlane(tid0 >> 6);
   // m[0], m[1]: this thread's gather slots (gather_order: present rows first;
-  // slot tid and 768 + tid, the latter only below 1024): row << 16 |
+  // slot tid and, with 12 waves, 768 + tid, the latter only below 1024): row << 16 |
   // mul_index(E[row]), low half 0xFFFF = absent.  m[2], m[3]: the output rows
   // y = 4 lane + q of phase 5, 16 bits each: 0xFFFF = present, else
   // mul_index(E[y]).  Loaded one tile ahead.
   const auto load_meta = [&](uint64_t bw, uint32_t tid, uint32_t (&m)[4]) {
     const uint64_t pt = pattern ? pattern[bw] : bw;
     m[0] = order[bw * N + tid];
-    m[1] = tid + THREADS < uint32_t(N) ? order[bw * N + THREADS + tid] : 0xFFFFu;
+    if constexpr (F::SLOTS == 2) m[1] = tid + THREADS < uint32_t(N) ? order[bw * N + THREADS + tid] : 0xFFFFu;
     const uint32_t y0 = 4 * (tid & 63);
     const uint32_t p4 = *reinterpret_cast<const uint32_t *>(present + pt * N + y0);
     const uint2 e4 = *reinterpret_cast<const uint2 *>(elog + pt * N + y0);
@@ -279,8 +309,8 @@ __global__ void __launch_bounds__(THREADS) reconstruct_n1024x(
     uint32_t nxt;  // the next tile (SLOT)
     // ---- phase 1: gather + scale this thread's slots' rows (decode_main:
     // 174-177), 12 groups of 4 columns each into the groups' regions; absent
-    // rows as 0.  The first slot's row and E[v] table are requested before
-    // the tile barrier.
+    // rows as 0 (16 waves: one slot, 16 groups).  The first slot's row and
+    // E[v] table are requested before the tile barrier.
     {
       uint32_t w[ROW_WORDS] = {};  // (defined on every path: not carried across tiles)
       Tab RT = {};
@@ -297,7 +327,7 @@ __global__ void __launch_bounds__(THREADS) reconstruct_n1024x(
             w[4 * q + 3] = d.w;
           }
         } else {  // the payload's last tile
-          load_row_tail96(row, uint32_t(avail), w);
+          load_row_tail<ROW_WORDS>(row, uint32_t(avail), w);
         }
         load_tab(t.mtab_tin, meta[half] & 0xffffu, RT);  // scaled into tower coordinates
       };
@@ -306,7 +336,7 @@ __global__ void __launch_bounds__(THREADS) reconstruct_n1024x(
       nxt = __builtin_amdgcn_readfirstlane(*slot);
       if (tid0 == 0) taken = gridDim.x + atomicAdd(tick, 1u);  // the tile after nxt
 #pragma unroll
-      for (int half = 0; half < 2; ++half) {
+      for (int half = 0; half < F::SLOTS; ++half) {
         if (half == 1 && tid >= uint32_t(N - THREADS)) break;  // (uniform per wave)
         const uint32_t v = meta[half] >> 16;
         const bool on = (meta[half] & 0xffffu) != 0xffffu;
@@ -314,12 +344,14 @@ __global__ void __launch_bounds__(THREADS) reconstruct_n1024x(
         uint32_t l[WAVES], h[WAVES];
 #pragma unroll
         for (int g = 0; g < WAVES; ++g) l[g] = h[g] = 0;
-        if (on) {  // one divergent branch for the 12 groups
-          if (v < uint32_t(K)) {  // phase 5's copy of a received data row
+        if (on) {  // one divergent branch for the tile's groups
+          if constexpr (F::STAGED) {
+            if (v < uint32_t(K)) {  // phase 5's copy of a received data row
 #pragma unroll
-            for (int j = 0; j < ROW_WORDS / 4; ++j)
-              *reinterpret_cast<__attribute__((address_space(3))) v4u *>(uintptr_t(stg_row(v) + 16 * j)) =
-                  v4u{w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]};
+              for (int j = 0; j < ROW_WORDS / 4; ++j)
+                *reinterpret_cast<__attribute__((address_space(3))) v4u *>(uintptr_t(stg_row<WAVES>(v) + 16 * j)) =
+                    v4u{w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]};
+            }
           }
 #pragma unroll
           for (int g = 0; g < WAVES; ++g) {  // columns 4g..4g+3: words (h0 l0 h1 l1)(h2 l2 h3 l3)
@@ -386,8 +418,24 @@ __global__ void __launch_bounds__(THREADS) reconstruct_n1024x(
     ipassC2(s);
 
     // phase-5 operands requested now, consumed after the derivative and the
-    // FFT: E[y] of this lane's erased output rows y = 4 lane + q (and the
-    // received ones)
+    // FFT.  16 waves: the received rows y = 4 lane + q < 256 themselves, this
+    // wave's 4 columns: an aligned 8-B word whose first two bytes are inside
+    // the row (cbase < ncols), so it stays on the row's page and, a data row
+    // never being the buffer's last, inside the buffer.  Absent rows are not
+    // read.  (Requested before the tables: after them, or one by one between
+    // them, the compiler spills 46 dwords.)
+    uint2 RV[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const uint32_t m = (meta[2 + (q >> 1)] >> (16 * (q & 1))) & 0xFFFFu;
+      RV[q] = make_uint2(0, 0);
+      if constexpr (!F::STAGED) {
+        if (m == 0xFFFFu)
+          RV[q] = *reinterpret_cast<const uint2 *>(SH + uint64_t(4 * lane + uint32_t(q)) * sstride + 2 * cbase);
+      }
+    }
+    // E[y] of this lane's erased output rows y = 4 lane + q (and the received
+    // ones)
     Tab T5[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -522,7 +570,8 @@ __global__ void __launch_bounds__(THREADS) reconstruct_n1024x(
         if (m != 0xFFFFu) {
           mul_acc(ql[q], qh[q], T5[q], ol[q], oh[q]);
         } else {
-          const uint2 rv = lds_ld2(stg_row(4 * lane + uint32_t(q)) + 8 * wave_s);
+          uint2 rv = RV[q];
+          if constexpr (F::STAGED) rv = lds_ld2(stg_row<WAVES>(4 * lane + uint32_t(q)) + 8 * wave_s);
           oh[q] = vperm(rv.y, rv.x, 0x06040200u);
           ol[q] = vperm(rv.y, rv.x, 0x07050301u);
         }
@@ -552,19 +601,28 @@ __global__ void __launch_bounds__(THREADS) reconstruct_n1024x(
 size_t n1024_tick_offset(const CodeParams &p, size_t batch) { return (gather_order_bytes(p, batch) + 255) / 256 * 256; }
 size_t n1024_scratch_bytes(const CodeParams &p, size_t batch) { return n1024_tick_offset(p, batch) + 256; }
 
-static_assert(size_t(COLS) == kN1024xMinCols, "choose_reconstruct: at least one whole tile");
+static_assert(size_t(Form<12>::COLS) == kN1024xMinCols, "choose_reconstruct: at least one whole tile");
+static_assert(size_t(Form<16>::COLS) <= kN1024x16MinCols, "n1024x_waves: at least one whole tile");
 
-hipError_t launch_reconstruct_n1024x(const CodeParams &p, const DevTables &t,
-                                     const uint8_t *d_shards, size_t slen, size_t sstride,
-                                     const uint8_t *d_present, const uint16_t *d_err_log,
-                                     const uint32_t *d_pattern, size_t batch, uint8_t *d_out,
-                                     size_t ostride, void *scratch, hipStream_t s) {
+// the form launch_reconstruct_n1024x runs: 16 waves from kN1024x16MinCols
+// columns, 12 below and where ECCR_AMD_RECON_WAVES=12 is set
+int n1024x_waves(size_t slen) {
+  return !recon_overrides().waves12 && slen / 2 >= kN1024x16MinCols ? 16 : 12;
+}
+
+namespace {
+template <int WAVES>
+hipError_t launch_form(const CodeParams &p, const DevTables &t, const uint8_t *d_shards, size_t slen,
+                       size_t sstride, const uint8_t *d_present, const uint16_t *d_err_log,
+                       const uint32_t *d_pattern, size_t batch, uint8_t *d_out, size_t ostride,
+                       void *scratch, hipStream_t s) {
+  using F = Form<WAVES>;
   int cus = 0;
-  if (!t.cimg || !scratch || slen / 2 < size_t(COLS)) return hipErrorInvalidValue;
-  if (const hipError_t e = prepare_kernel(reinterpret_cast<const void *>(&reconstruct_n1024x), LDS_BYTES, &cus);
+  if (!t.cimg || !scratch || slen / 2 < size_t(F::COLS)) return hipErrorInvalidValue;
+  if (const hipError_t e = prepare_kernel(reinterpret_cast<const void *>(&reconstruct_n1024x<WAVES>), F::LDS_BYTES, &cus);
       e != hipSuccess)
     return e;
-  const size_t tiles = (slen / 2 + COLS - 1) / COLS * batch;
+  const size_t tiles = (slen / 2 + F::COLS - 1) / F::COLS * batch;
   if (tiles + 4096 >= (size_t(1) << 32)) return hipErrorInvalidValue;  // 32-bit tile tickets
   uint32_t *order = static_cast<uint32_t *>(scratch);  // n1024_scratch_bytes(p, batch)
   uint32_t *tick = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(scratch) + n1024_tick_offset(p, batch));
@@ -573,10 +631,23 @@ hipError_t launch_reconstruct_n1024x(const CodeParams &p, const DevTables &t,
     return e;
   if (const hipError_t e = launch_zero_counters(tick, sizeof(uint32_t), s); e != hipSuccess) return e;
   const unsigned grid = unsigned(tiles < size_t(cus) ? tiles : size_t(cus));
-  hipLaunchKernelGGL(reconstruct_n1024x, dim3(grid), dim3(THREADS), LDS_BYTES, s, d_shards, uint64_t(slen),
-                     uint64_t(sstride), d_present, d_err_log, d_pattern, order, d_out, uint64_t(ostride),
-                     int(p.nv), uint32_t(batch), tick, t);
+  hipLaunchKernelGGL(reconstruct_n1024x<WAVES>, dim3(grid), dim3(F::THREADS), F::LDS_BYTES, s, d_shards,
+                     uint64_t(slen), uint64_t(sstride), d_present, d_err_log, d_pattern, order, d_out,
+                     uint64_t(ostride), int(p.nv), uint32_t(batch), tick, t);
   return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_reconstruct_n1024x(const CodeParams &p, const DevTables &t,
+                                     const uint8_t *d_shards, size_t slen, size_t sstride,
+                                     const uint8_t *d_present, const uint16_t *d_err_log,
+                                     const uint32_t *d_pattern, size_t batch, uint8_t *d_out,
+                                     size_t ostride, void *scratch, hipStream_t s) {
+  return n1024x_waves(slen) == 16
+             ? launch_form<16>(p, t, d_shards, slen, sstride, d_present, d_err_log, d_pattern, batch, d_out,
+                               ostride, scratch, s)
+             : launch_form<12>(p, t, d_shards, slen, sstride, d_present, d_err_log, d_pattern, batch, d_out,
+                               ostride, scratch, s);
 }
 
 }  // namespace ecamd

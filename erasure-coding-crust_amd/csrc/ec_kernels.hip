@@ -732,6 +732,7 @@ const ReconOverrides &recon_overrides() {
     const char *w = std::getenv("ECCR_AMD_RECON_WAVES"), *k = std::getenv("ECCR_AMD_RECON_PACKED");
     ReconOverrides r;
     r.waves8 = w && w[0] == '8';
+    r.waves12 = w && w[0] == '1' && w[1] == '2';
     r.force_packed = k && k[0] == '1';
     return r;
   }();

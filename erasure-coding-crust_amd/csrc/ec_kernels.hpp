@@ -128,13 +128,14 @@ const char *kernel_name(Kernel k);  // the enumerator's name; nullptr for invali
 
 // Pure host functions: the pointers are only looked at as addresses, no device
 // is needed.  recon_overrides(): the experiment switches ECCR_AMD_RECON_WAVES=8
-// (waves8: the 8-wave kernel where the 12-wave one applies) and
+// (waves8: the 8-wave kernel where reconstruct_n1024x applies), =12 (waves12:
+// reconstruct_n1024x in its 12-wave form at every size, n1024x_waves) and
 // ECCR_AMD_RECON_PACKED=1 (force_packed: reconstruct_n1024 packed at every
 // size), read from the environment once per process.
 Kernel choose_encode(const CodeParams &p, size_t payload_len, size_t payload_stride, size_t batch,
                      uintptr_t payloads, uintptr_t shards, size_t shard_stride);
 struct ReconOverrides {
-  bool waves8 = false, force_packed = false;
+  bool waves8 = false, waves12 = false, force_packed = false;
 };
 const ReconOverrides &recon_overrides();
 Kernel choose_reconstruct(const CodeParams &p, size_t shard_len, size_t shard_stride, size_t batch,
@@ -201,8 +202,12 @@ hipError_t warm_encode_tiny(hipStream_t s);  // device set-up: the first launche
 bool k256_applicable(const CodeParams &p);
 // tile sizes the choosers test (static_asserts beside the kernels): pieces per
 // tile of the unpacked k = 256 encodes' dispatch, columns per tile of
-// reconstruct_n1024<false>, and the fewest columns reconstruct_n1024x takes
-constexpr size_t kK256Tile = 128, kN1024Cols = 32, kN1024xMinCols = 48;
+// reconstruct_n1024<false>, the fewest columns reconstruct_n1024x takes, and
+// the fewest from which it runs its 16-wave form (n1024x_waves: measured; at
+// 96 and 144 columns, two and three whole 12-wave tiles, the 12-wave form is
+// still the faster one, from 145 on the 16-wave form at every count measured,
+// profiles/n1024x16/)
+constexpr size_t kK256Tile = 128, kN1024Cols = 32, kN1024xMinCols = 48, kN1024x16MinCols = 145;
 // encode_k256_packed (choose_encode): the packed (flattened-piece,
 // any-alignment) kernel for small payloads or pitches the unpacked kernels
 // cannot take; no scratch
@@ -259,8 +264,10 @@ hipError_t launch_reconstruct_n1024(const CodeParams &p, const DevTables &t, boo
                                     const uint8_t *d_present, const uint16_t *d_err_log,
                                     const uint32_t *d_pattern, size_t batch, uint8_t *d_out,
                                     size_t ostride, void *scratch, hipStream_t s);
-// the 12-wave form (dec_n1024x.hip) for the unpacked case; both take
-// n1024_scratch_bytes (the gather order + the 12-wave form's tile counter)
+// reconstruct_n1024x (dec_n1024x.hip) for the unpacked case, in its 12- or
+// 16-wave form: n1024x_waves(shard_len), a pure host function.  Every n = 1024
+// form takes n1024_scratch_bytes (the gather order + n1024x's tile counter)
+int n1024x_waves(size_t slen);
 size_t n1024_scratch_bytes(const CodeParams &p, size_t batch);
 size_t n1024_tick_offset(const CodeParams &p, size_t batch);
 hipError_t launch_reconstruct_n1024x(const CodeParams &p, const DevTables &t,

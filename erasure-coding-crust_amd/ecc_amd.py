@@ -123,6 +123,7 @@ def lib():
                                                                  ul, vp]),
             "ECCR_AMD_encode_kernel": (C.c_char_p, [ul, vp, ul, ul, ul, vp, ul]),
             "ECCR_AMD_reconstruct_kernel": (C.c_char_p, [ul, vp, ul, ul, vp, vp, ul, vp, ul]),
+            "ECCR_AMD_reconstruct_n1024x_waves": (C.c_int, [ul]),
             "ECCR_AMD_locator_cache_stats": (NPRSResult, [up, up]),
             "ECCR_AMD_encode_workspace_bytes": (ul, [ul, ul, ul]),
             "ECCR_AMD_error_locator_workspace_bytes": (ul, [ul, ul]),
@@ -379,6 +380,12 @@ def reconstruct_kernel(nv, d_shards, shard_len_, shard_stride, d_present, d_err_
                                           _p(d_present), _p(d_err_log), batch, _p(d_out),
                                           out_stride)
     return None if r is None else r.decode()
+
+
+def reconstruct_n1024x_waves(shard_len_: int) -> int:
+    """Waves per workgroup (12 or 16) reconstruct_n1024x runs with at this shard length
+    (host-only; ECCR_AMD_RECON_WAVES=12 in the environment at start: 12 everywhere)."""
+    return int(lib().ECCR_AMD_reconstruct_n1024x_waves(shard_len_))
 
 
 def locator_cache_stats():

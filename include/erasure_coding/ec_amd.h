@@ -175,6 +175,11 @@ const char *ECCR_AMD_reconstruct_kernel(unsigned long n_validators, const uint8_
                                         const uint8_t *d_present, const uint16_t *d_err_log,
                                         unsigned long batch, const uint8_t *d_out,
                                         unsigned long out_stride);
+/* Waves per workgroup (12 or 16) of reconstruct_n1024x for shards of shard_len
+ * bytes, where ECCR_AMD_reconstruct_kernel names that kernel: 16 from 145
+ * shard columns (290 bytes) upward, 12 below, and 12 everywhere in a process
+ * started with ECCR_AMD_RECON_WAVES=12.  Host-only. */
+int ECCR_AMD_reconstruct_n1024x_waves(unsigned long shard_len);
 
 /* Hits / misses of the per-device locator cache of ECCR_reconstruct (the
  * locator of a pattern is computed once and reused while it is among the 64

@@ -161,7 +161,8 @@ for k in kinds:
         decx = rep(decx, "        if (on) {  // one divergent branch", "        if (meta[half] == 0x12345678u) {  //")
         extra["dec_n1024x.hip"] = decx
     elif k == "xnorv":
-        decx = rep(decx, "          const uint2 rv = lds_ld2(stg_row(4 * lane + uint32_t(q)) + 8 * wave_s);\n",
+        decx = rep(decx, "          uint2 rv = RV[q];\n"
+                         "          if constexpr (F::STAGED) rv = lds_ld2(stg_row<WAVES>(4 * lane + uint32_t(q)) + 8 * wave_s);\n",
                    "          const uint2 rv = make_uint2(lane, uint32_t(q));\n")
         extra["dec_n1024x.hip"] = decx
     elif k == "xwdyn":

@@ -27,11 +27,11 @@ if "RB" in knobs:
     s = rep(s, "constexpr int RING_B = 3;", f"constexpr int RING_B = {knobs['RB']};")
 if knobs.get("PRIO") in ("1", "2"):
     lead = "2u - uint32_t(phase)" if knobs["PRIO"] == "1" else "uint32_t(phase)"
-    s = rep(s, "}  // namespace\n\n__global__",
+    s = rep(s, "}  // namespace\n\ntemplate <int WAVES>\n__global__",
             "__device__ __forceinline__ void prio3(uint32_t wave_s, int phase) {\n"
             f"  const uint32_t lead = {lead};\n"
             "  if (phase < 3 && (wave_s >> 2) == lead) __builtin_amdgcn_s_setprio(2);\n"
-            "  else __builtin_amdgcn_s_setprio(0);\n}\n\n}  // namespace\n\n__global__")
+            "  else __builtin_amdgcn_s_setprio(0);\n}\n\n}  // namespace\n\ntemplate <int WAVES>\n__global__")
     s = rep(s, "      ipassA2(s, lane);", "      prio3(wave_s, 0);\n      ipassA2(s, lane);")
     s = rep(s, "      ipassB2(s, lane);", "      prio3(wave_s, 1);\n      ipassB2(s, lane);")
     s = rep(s, "    // layout C: r bit0", "    prio3(wave_s, 2);\n    // layout C: r bit0")
