@@ -30,8 +30,6 @@ using OutTabs = LdsTabs<128>;  // E[y], y < k <= 128, own area: filled once per 
 constexpr int LDS_BYTES = Tabs::kBytes + WAVES * REG_BYTES + OutTabs::kBytes;
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 
-__device__ __forceinline__ uint32_t mul_index(uint32_t c) { return c == 65535u ? 0u : c; }
-
 // inverse pass over register bits 0..NS-1 (position bits B0..) of
 // the local index pos & (n - 1); lb = tlin of the (masked) lane part
 // When the pass holds the top local bit (B0 + NS == L), the lane part of a

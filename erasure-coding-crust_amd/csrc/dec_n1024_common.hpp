@@ -172,8 +172,6 @@ __device__ __forceinline__ void swap_bit(uint32_t &x, uint32_t &y, int b, bool h
   else y = recv;
 }
 
-__device__ __forceinline__ uint32_t mul_index(uint32_t c) { return c == 65535u ? 0u : c; }
-
 // 8 shard bytes at any even address, zero past `avail` (1..8 bytes valid
 // from p): three dword loads, each clamped to the dword that holds the last
 // wanted byte (so nothing past the row is touched), funnel-shifted by

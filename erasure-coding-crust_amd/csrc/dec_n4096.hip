@@ -38,8 +38,6 @@ constexpr uint32_t SLOT = Tabs::kBytes + WAVES * REG_BYTES;  // the next tile's 
 constexpr int LDS_BYTES = int(SLOT + 16);
 static_assert(LDS_BYTES <= 160 * 1024 && Tabs::kBytes == kTabImageBytes, "LDS budget");
 
-__device__ __forceinline__ uint32_t mul_index(uint32_t c) { return c == 65535u ? 0u : c; }
-
 // multiplier logs (65535 = multiply by zero) of the linearised cross-quarter part
 // The data runs in tower coordinates; every p_q / k_q is a
 // subfield element (skews 1023 / 2047 / 3071 are 0, 0 and 2: p, k in {0, 1, 2, 3}),

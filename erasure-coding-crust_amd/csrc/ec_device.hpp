@@ -28,6 +28,14 @@ __device__ __forceinline__ uint32_t vperm(uint32_t hi, uint32_t lo, uint32_t sel
   return __builtin_amdgcn_perm(hi, lo, sel);
 }
 
+// byte-planar group (4 pieces / columns) -> big-endian u16 x4 (in order)
+__device__ __forceinline__ uint2 to_be(uint32_t l, uint32_t h) {
+  return make_uint2(vperm(l, h, 0x05010400u), vperm(l, h, 0x07030602u));
+}
+
+// multiply-table index of a log-domain constant: 65535 == 0 (mod 65535)
+__device__ __forceinline__ uint32_t mul_index(uint32_t log_c) { return log_c == 65535u ? 0u : log_c; }
+
 // Workgroup barrier that orders LDS only: waits for this wave's LDS operations
 // (lgkmcnt) but NOT for outstanding global stores/loads, unlike __syncthreads()
 // whose fence drains vmcnt and would serialize the HBM write stream with the

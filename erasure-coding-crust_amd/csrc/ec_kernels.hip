@@ -399,10 +399,6 @@ __global__ void __launch_bounds__(kBlock) pattern_broadcast(const uint32_t *__re
   for (int i = threadIdx.x; i < n; i += kBlock) dst[i] = src[i];
 }
 
-__device__ __forceinline__ uint32_t mul_index(uint32_t log_c) {  // 65535 == 0 (mod 65535)
-  return log_c == 65535u ? 0u : log_c;
-}
-
 // reed-solomon.hpp:83-134 + poly_encoder.hpp:118-215 for 4*G shard positions
 __global__ void __launch_bounds__(kBlock) reconstruct_g(
     const uint8_t *__restrict__ shards, uint64_t slen, uint64_t sstride,

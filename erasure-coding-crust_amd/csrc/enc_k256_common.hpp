@@ -1,8 +1,10 @@
 // enc_k256_common.hpp — pieces shared by the k = 256 encode kernels
-// (enc_k256.hip: the n = 1024 packed and n = 2048 forms; enc_k256w.hip: the
-// n = 1024 two-workgroups-per-CU form).  One byte-planar group of 4 pieces
-// per instance (lanes 0-31 / 32-63), 8 positions of the 256-point transforms
-// per lane in registers, wave-private LDS exchanges between the radix-8 passes.
+// (enc_k256.hip: the n = 1024 packed and n = 2048 forms) and, through
+// enc_w_common.hpp, by the two-workgroups-per-CU kernels, whose layouts are
+// the k = 256 ones (enc_k256w.hip, enc_kw.hip, enc_k512w.hip).  One
+// byte-planar group of 4 pieces per instance (lanes 0-31 / 32-63), 8 positions
+// of the 256-point transforms per lane in registers, wave-private LDS
+// exchanges between the radix-8 passes.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -126,11 +128,6 @@ __device__ __forceinline__ void exchange(State &s, uint8_t *xch, const XBase &xb
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
-}
-
-// byte-planar group (4 pieces) -> big-endian u16 x4 (pieces 0..3 in order)
-__device__ __forceinline__ uint2 to_be(uint32_t l, uint32_t h) {
-  return make_uint2(vperm(l, h, 0x05010400u), vperm(l, h, 0x07030602u));
 }
 
 // 16 payload bytes at any address, zero past `avail` (bytes valid from p):

@@ -2,8 +2,8 @@
 // 46..765, the Polkadot validator counts of today among them) and k = 256 at
 // n = 2048 (n_validators 1025..1533), two 8-wave workgroups per CU.
 //
-// encode_k256w's model (enc_k256w.hip): per piece (2 k
-// payload bytes = k symbols) IFFT_k at index 0, then FFT_k at each coset k j
+// encode_k256w's model (enc_k256w.hip, its shared code in enc_w_common.hpp;
+// DESIGN.md §5.1, §5.7): per piece (2 k payload bytes = k symbols) IFFT_k at index 0, then FFT_k at each coset k j
 // below n_validators (encodeLow, poly_encoder.hpp:217-240), radix-8 register
 // passes in tower coordinates, wave-private LDS exchanges.  A wave holds NG =
 // 512 / k byte-planar groups of 4 pieces; a group's k positions lie over k / 8
@@ -22,22 +22,12 @@
 //    extension image brought in by LDS-DMA, as in enc_k512w.hip (74 KB);
 //  * tiles of 8 NG pieces per wave (32 KB of payload), shard-row segments of
 //    64 NG bytes stored as 16 B per lane (two groups of one wave).
-#include <hip/hip_runtime.h>
-
-#include "ec_device.hpp"
-#include "ec_kernels.hpp"
-#include "cimg.hpp"
-#include "enc_k256_common.hpp"
-
-#include <type_traits>
+#include "enc_w_common.hpp"
 
 namespace ecamd {
 namespace {
 
-constexpr int WAVES = 8;
-constexpr int THREADS = 64 * WAVES;
 constexpr uint32_t XCH0 = kCImgBytes;        // the wave regions follow the tables
-constexpr uint32_t XCH_BYTES = 4096;
 constexpr uint32_t SLOT = XCH0 + WAVES * XCH_BYTES;  // the next tile's index
 // k = 256 (n = 2048 only): the extension tables of cosets 4..7 (stage 0,
 // elements 512..1023: ec_kernels.hpp kEImg256*) after the slot
@@ -46,7 +36,6 @@ template <int M>
 constexpr int lds_bytes() { return int(M == 8 ? EXT8 + kEImg256Bytes : SLOT + 16); }
 static_assert(2 * lds_bytes<8>() <= 160 * 1024, "two workgroups per CU");
 static_assert(XCH0 % (2 * XCH_BYTES) == 0, "XOR-addressed regions");
-static_assert(kCImgBytes % (16 * THREADS) == 0, "whole image chunks per thread");
 
 template <int M>
 struct Geo {
@@ -60,130 +49,11 @@ struct Geo {
   static_assert(M >= 4 && M <= 8, "k = 16 .. 256");
 };
 
-struct XLanes {
-  uint32_t l0, l1, l2;
+// Stage 0 of cosets 4..7 at k = 256, n = 2048: a general table of the coset's
+// extension image in LDS (enc_w_common.hpp ftab)
+struct Ext0 : ExtKind {
+  static constexpr uint32_t BASE = EXT8, PLANE = kEImg256Bytes / 5;
 };
-template <int B0>
-__device__ __forceinline__ XLanes xlanes(uint32_t base) {
-  return {cimg_lin(base >> (B0 + 1)), cimg_lin(base >> (B0 + 2)), cimg_lin(base >> (B0 + 3))};
-}
-
-// inverse radix-8 pass at index 0: every element < 64 (subfield)
-template <int B0>
-__device__ __forceinline__ void ipass(State &s, uint32_t base) {
-  const XLanes x = xlanes<B0>(base);
-  SubTab Ta0, Tb0, Ta1, Tb1, Ta2;
-  ctab(x.l0, cimg_lin(0), Ta0);
-  ctab(x.l0, cimg_lin(1), Tb0);
-  ibfly(s, 0, 1, Ta0);
-  ctab(x.l0, cimg_lin(2), Ta0);
-  ibfly(s, 2, 3, Tb0);
-  ctab(x.l0, cimg_lin(3), Tb0);
-  ibfly(s, 4, 5, Ta0);
-  ctab(x.l1, cimg_lin(0), Ta1);
-  ibfly(s, 6, 7, Tb0);
-  ctab(x.l1, cimg_lin(1), Tb1);
-  ibfly(s, 0, 2, Ta1);
-  ibfly(s, 1, 3, Ta1);
-  ctab(x.l2, cimg_lin(0), Ta2);
-  ibfly(s, 4, 6, Tb1);
-  ibfly(s, 5, 7, Tb1);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) ibfly(s, r, r + 4, Ta2);
-}
-
-// Table kinds of a stage: the compact image's subfield / F9 / general entries
-// (SubTab, F9Tab, Tab), or (k = 256 at n = 2048, stage 0 of cosets 4..7) a
-// general table of the coset's extension image in LDS (Ext0)
-struct Ext0 {};
-template <typename K_>
-struct TabOf {
-  using type = K_;
-};
-template <>
-struct TabOf<Ext0> {
-  using type = Tab;
-};
-// table of element x = lane part lt ^ block part r ^ uniform part u (each the
-// cimg_lin of its bits); an extension table sits at the coset-local entry
-// (u, the coset's offset bits, dropped)
-template <typename K_>
-__device__ __forceinline__ void ftab(uint32_t lt, uint32_t r, uint32_t u, typename TabOf<K_>::type &T) {
-  if constexpr (std::is_same_v<K_, Ext0>) {
-    const uint32_t a = lt ^ r;
-#pragma unroll
-    for (int q = 4; q >= 0; --q) {
-      const v4u v = lds_r128(a + EXT8 + uint32_t(q) * (kEImg256Bytes / 5));
-      T.t[4 * q] = v.x;
-      T.t[4 * q + 1] = v.y;
-      T.t[4 * q + 2] = v.z;
-      T.t[4 * q + 3] = v.w;
-    }
-  } else {
-    ctab(lt, r ^ u, T);
-  }
-}
-
-// forward radix-8 pass at index off: stages B0+2, B0+1, B0 with table kinds
-// K2, K1, K0 (known per coset)
-template <int B0, typename K2, typename K1, typename K0>
-__device__ __forceinline__ void fpass(State &s, uint32_t base, uint32_t off) {
-  const XLanes x = xlanes<B0>(base);
-  const uint32_t u0 = cimg_lin(off >> (B0 + 1)), u1 = cimg_lin(off >> (B0 + 2)), u2 = cimg_lin(off >> (B0 + 3));
-  typename TabOf<K2>::type Ta2;
-  typename TabOf<K1>::type Ta1, Tb1;
-  typename TabOf<K0>::type Ta0, Tb0;
-  ftab<K2>(x.l2, 0u, u2, Ta2);
-  ftab<K1>(x.l1, 0u, u1, Tb1);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) fbfly(s, r, r + 4, Ta2);
-  ftab<K1>(x.l1, cimg_lin(1), u1, Ta1);
-  fbfly(s, 0, 2, Tb1);
-  fbfly(s, 1, 3, Tb1);
-  ftab<K0>(x.l0, 0u, u0, Tb0);
-  fbfly(s, 4, 6, Ta1);
-  fbfly(s, 5, 7, Ta1);
-  ftab<K0>(x.l0, cimg_lin(1), u0, Ta0);
-  fbfly(s, 0, 1, Tb0);
-  ftab<K0>(x.l0, cimg_lin(2), u0, Tb0);
-  fbfly(s, 2, 3, Ta0);
-  ftab<K0>(x.l0, cimg_lin(3), u0, Ta0);
-  fbfly(s, 4, 5, Tb0);
-  fbfly(s, 6, 7, Ta0);
-}
-
-// ---- layout C for k = 256 (register bit 0 = p6, bit 1 = p7, bit 2 = p5):
-// the elements of stages 6, 7 are lane-uniform (enc_k256w.hip ipassC0w /
-// fpassCw).  IFFT at index 0: stage 7 (x = 0) and stage 6's p7 = 0 block (x =
-// 0) are b ^= a only; stage 6's p7 = 1 block has x = 1.
-__device__ __forceinline__ void ipassC8(State &s) {
-  SubTab Tb;
-  ctab(0u, cimg_lin(1), Tb);
-  bxor(s, 0, 1);
-  bxor(s, 4, 5);
-  ibfly(s, 2, 3, Tb);
-  ibfly(s, 6, 7, Tb);
-  bxor(s, 0, 2);
-  bxor(s, 1, 3);
-  bxor(s, 4, 6);
-  bxor(s, 5, 7);
-}
-// FFT stages 7, 6 at index off from the IFFT coefficients c: stage 7 x = off
-// >> 8, stage 6 x = off >> 7 | p7
-__device__ __forceinline__ void fpassC8(State &s, const State &c, uint32_t off) {
-  SubTab Ta, Tb;
-  ctab(0u, cimg_lin(off >> 8), Ta);
-  ctab(0u, cimg_lin(off >> 7), Tb);
-  fbfly_from(s, c, 0, 2, Ta);
-  fbfly_from(s, c, 1, 3, Ta);
-  fbfly_from(s, c, 4, 6, Ta);
-  fbfly_from(s, c, 5, 7, Ta);
-  ctab(0u, cimg_lin((off >> 7) | 1u), Ta);
-  fbfly(s, 0, 1, Tb);
-  fbfly(s, 4, 5, Tb);
-  fbfly(s, 2, 3, Ta);
-  fbfly(s, 6, 7, Ta);
-}
 
 // ---- layout B for M <= 6: registers p3, p4, p5 as far as they are positions
 // (the others group bits), no lane part: every element is x = (register
@@ -258,25 +128,6 @@ __device__ __forceinline__ void fpassB_u(State &s, const State &c, uint32_t off)
   }
 }
 
-// wave-private exchange at the wave's region folded into the lane bases (bits
-// >= 12), the bases laundered so the cell addresses are formed here
-template <Layout FROM, Layout TO>
-__device__ __forceinline__ void xchg(State &s, XBase xb) {
-  asm volatile("" : "+v"(xb.a), "+v"(xb.b), "+v"(xb.c));
-#pragma unroll
-  for (int r = 0; r < 8; ++r) lds_st2(xcell<FROM>(xb, r), make_uint2(s.l[0][r], s.h[0][r]));
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-#pragma unroll
-  for (int r = 0; r < 8; ++r) {
-    const uint2 v = lds_ld2(xcell<TO>(xb, r));
-    s.l[0][r] = v.x;
-    s.h[0][r] = v.y;
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 // ---- own-region staging: wave w stages its NG groups x k rows in its own
 // 4 KB region, 8 B per (row v, group g) at slot (v NG + g) ^ (v >> 3) << (8 -
 // M) ^ ((w << (9 - M)) & 31).  Layout-A writes (rows 8 q + r; 32 lanes = the
@@ -301,81 +152,22 @@ __device__ __forceinline__ void stage_own(const State &s, uint32_t q, uint32_t g
   for (int r = 0; r < 8; ++r) lds_st2(a ^ soff<M>(uint32_t(r), 0, 0), to_be(s.l[0][r], s.h[0][r]));
 }
 
-// all waves: rows [s0, s0 + k) from the 8 regions -> shards.  Chunk G = it *
-// 512 + thread: row v = G / RC, chunk c = G % RC (16 B = pieces 8c..8c+7 =
-// groups 2h, 2h + 1 of wave c / (NG / 2)).  Fast path (uniform): 16-B aligned
-// rows, the whole tile inside the payload, all k rows below n_validators -- 4
-// streaming 16-B stores per lane.
+// the row stores' geometry (enc_w_common.hpp store_own): chunk it * 512 +
+// thread: row v = chunk / RC, chunk c = chunk % RC (16 B = pieces 8c..8c+7 =
+// groups 2h, 2h + 1 of wave c / (NG / 2))
 template <int M>
-__device__ __forceinline__ bool store_fast(const uint8_t *SH, uint64_t sstride, uint32_t s0, int nv,
-                                           uint64_t piece0, uint64_t npieces) {
-  return ((sstride | reinterpret_cast<uintptr_t>(SH)) & 15) == 0 && piece0 + Geo<M>::TILE <= npieces &&
-         int(s0) + int(Geo<M>::K) <= nv;
-}
-
-template <int M, typename Then>
-__device__ __forceinline__ void store_own(uint8_t *SH, uint64_t sstride, uint32_t s0, int nv,
-                                          uint64_t piece0, uint64_t npieces, uint32_t wave,
-                                          uint32_t lane, Then &&then) {
+struct Rows {
   using G = Geo<M>;
-  asm volatile("" : "+v"(lane));  // recomputed here, not kept live across the FFTs
-  const uint32_t t = wave * 64 + lane;
-  const uint32_t v0 = t / G::RC, c = t % G::RC;  // it = 0
-  const uint32_t cw = c / (G::NG / 2), h = c % (G::NG / 2);
-  const uint32_t ra = XCH0 + cw * XCH_BYTES + soff<M>(v0, 2 * h, cw);  // 16-B aligned: groups 2h, 2h + 1
-  constexpr uint32_t VSTEP = 512 / G::RC;  // rows per iteration
-  if (store_fast<M>(SH, sstride, s0, nv, piece0, npieces)) {
-    uint8_t *dst = SH + uint64_t(s0 + v0) * sstride + 2 * (piece0 + 8 * c);
-    const uint64_t dstep = uint64_t(VSTEP) * sstride;
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {  // soff is GF(2)-linear in v = it * VSTEP | v0
-      const v4u val = lds_r128(ra ^ soff<M>(uint32_t(it) * VSTEP, 0, 0));
-      __builtin_nontemporal_store(val, reinterpret_cast<v4u *>(dst + it * dstep));
-    }
-    then();
-    asm volatile("; store_own fast path end" ::: "memory");
-    return;
+  static constexpr int TILE = G::TILE, K = G::K;
+  static constexpr uint32_t VSTEP = 512 / G::RC;
+  __device__ static __forceinline__ RowLane lane_role(uint32_t wave, uint32_t lane) {
+    const uint32_t t = wave * 64 + lane;
+    const uint32_t v0 = t / G::RC, c = t % G::RC;
+    const uint32_t cw = c / (G::NG / 2), h = c % (G::NG / 2);
+    return {v0, c, XCH0 + cw * XCH_BYTES + soff<M>(v0, 2 * h, cw)};  // 16-B aligned: groups 2h, 2h + 1
   }
-  const uint64_t p = piece0 + 8 * c;
-  const bool wide = ((sstride | reinterpret_cast<uintptr_t>(SH)) & 15) == 0;
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const uint32_t v = uint32_t(it) * VSTEP + v0;
-    const v4u val = lds_r128(ra ^ soff<M>(uint32_t(it) * VSTEP, 0, 0));
-    const uint32_t shard = s0 + v;
-    if (int(shard) >= nv) continue;
-    uint8_t *dst = SH + uint64_t(shard) * sstride + 2 * p;
-    if (p + 8 <= npieces) {
-      if (wide) {
-        *reinterpret_cast<v4u *>(dst) = val;
-      } else {
-        reinterpret_cast<uint2 *>(dst)[0] = make_uint2(val.x, val.y);
-        reinterpret_cast<uint2 *>(dst)[1] = make_uint2(val.z, val.w);
-      }
-    } else if (p < npieces) {
-      const uint32_t w[4] = {val.x, val.y, val.z, val.w};
-      for (uint64_t e = 0; e < npieces - p; ++e)
-        *reinterpret_cast<uint16_t *>(dst + 2 * e) = uint16_t(w[e >> 1] >> (16 * (e & 1)));
-    }
-  }
-  then();
-  asm volatile("; store_own slow path end" ::: "memory");
-}
-
-// 4 x 16 payload bytes (4 pieces, positions 8 q .. 8 q + 7) -> byte-planar
-// State (enc_k256w.hip to_state)
-__device__ __forceinline__ void to_state(const v4u (&d)[4], State &s) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const uint32_t D0 = d[0][j], D1 = d[1][j], D2 = d[2][j], D3 = d[3][j];
-    const uint32_t t0 = vperm(D1, D0, 0x05010400u), t1 = vperm(D1, D0, 0x07030602u);
-    const uint32_t u0 = vperm(D3, D2, 0x05010400u), u1 = vperm(D3, D2, 0x07030602u);
-    s.h[0][2 * j] = vperm(u0, t0, 0x05040100u);
-    s.l[0][2 * j] = vperm(u0, t0, 0x07060302u);
-    s.h[0][2 * j + 1] = vperm(u1, t1, 0x05040100u);
-    s.l[0][2 * j + 1] = vperm(u1, t1, 0x07060302u);
-  }
-}
+  __device__ static __forceinline__ v4u read(uint32_t a, int it) { return lds_r128(a ^ soff<M>(uint32_t(it) * VSTEP, 0, 0)); }
+};
 
 }  // namespace
 
@@ -393,14 +185,7 @@ __global__ void __launch_bounds__(THREADS, 4) encode_kw(const uint8_t *__restric
   const uint32_t tid0 = threadIdx.x;
   auto *slot = reinterpret_cast<__attribute__((address_space(3))) volatile uint32_t *>(uintptr_t(SLOT));
   if (tid0 == 0) *slot = tick ? atomicAdd(tick, 1u) : blockIdx.x;
-  {  // the compact image (32 KB), every load issued before the first store
-    constexpr int kPer = int(kCImgBytes / 16 / THREADS);
-    v4u v[kPer];
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) v[k] = reinterpret_cast<const v4u *>(cimg)[tid0 + k * THREADS];
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) reinterpret_cast<v4u *>(lds)[tid0 + k * THREADS] = v[k];
-  }
+  copy_cimg(lds, cimg, tid0);
   __syncthreads();
 
   const uint64_t npieces = slen / 2;
@@ -416,36 +201,10 @@ __global__ void __launch_bounds__(THREADS, 4) encode_kw(const uint8_t *__restric
   v4u d[4];
   State nxt;
   const auto fetch = [&](uint64_t fb, uint64_t fi) __attribute__((always_inline)) {
-    const uint8_t *FP = payloads + fb * pstride;
-    const uint64_t pw = fi * G::TILE + G::WP * wave_s;  // this wave's first piece (uniform)
     uint32_t ftid = tid0;
     asm volatile("" : "+v"(ftid));
     const uint32_t lane = ftid & 63, g = lane >> (M - 3), q = lane & G::QM;
-    if ((pw + G::WP) * 2 * K <= plen) {  // the wave's pieces inside the payload
-      const uint8_t *src = FP + (pw + 4 * g) * 2 * K + 16 * q;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) d[u] = *reinterpret_cast<const v4u *>(src + u * 2 * K);
-    } else if (pw < npieces) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const uint64_t off = (pw + 4 * g + u) * 2 * K + 16 * q;
-        uint32_t w[4] = {0, 0, 0, 0};
-        if (off + 16 <= plen) {
-          const v4u x = *reinterpret_cast<const v4u *>(FP + off);
-          w[0] = x.x;
-          w[1] = x.y;
-          w[2] = x.z;
-          w[3] = x.w;
-        } else {
-          for (uint64_t e = off; e < plen && e < off + 16; ++e)
-            w[(e - off) >> 2] |= uint32_t(FP[e]) << (8 * ((e - off) & 3));
-        }
-        d[u] = v4u{w[0], w[1], w[2], w[3]};
-      }
-    } else {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) d[u] = v4u{0, 0, 0, 0};
-    }
+    fetch_pieces<K>(payloads + fb * pstride, plen, npieces, fi * G::TILE + G::WP * wave_s, G::WP, g, q, d);
   };
   if (cur < total) {
     fetch(cur / tiles_pp, cur % tiles_pp);
@@ -471,7 +230,7 @@ __global__ void __launch_bounds__(THREADS, 4) encode_kw(const uint8_t *__restric
     uint8_t *SH = shards + b * uint64_t(nv) * sstride;
     // every store phase of this tile but possibly the last coset's takes the
     // fast path (4 stores per lane), or none does
-    [[maybe_unused]] const bool fast = store_fast<M>(SH, sstride, 0, nv, piece0, npieces);
+    [[maybe_unused]] const bool fast = store_fast<Rows<M>>(SH, sstride, 0, nv, piece0, npieces);
     // k = 256, n = 2048: coset j's extension image (10 x 1 KB) -> LDS, chunk i by
     // wave i % 8, issued after the previous coset's rows-staged barrier
     [[maybe_unused]] const auto dma_ext = [&](uint32_t j) __attribute__((always_inline)) {
@@ -487,15 +246,15 @@ __global__ void __launch_bounds__(THREADS, 4) encode_kw(const uint8_t *__restric
     const auto store = [&](uint32_t s0, bool last) __attribute__((always_inline)) {
       __builtin_amdgcn_s_setprio(1);
       if (last)
-        store_own<M>(SH, sstride, s0, nv, piece0, npieces, wave_s, lane,
+        store_own<Rows<M>>(SH, sstride, s0, nv, piece0, npieces, wave_s, lane,
                      [&]() __attribute__((always_inline)) { to_state(d, nxt); });
       else
-        store_own<M>(SH, sstride, s0, nv, piece0, npieces, wave_s, lane, [] {});
+        store_own<Rows<M>>(SH, sstride, s0, nv, piece0, npieces, wave_s, lane, [] {});
       __builtin_amdgcn_s_setprio(0);
     };
     const auto store_sys = [&]() __attribute__((always_inline)) {
       __builtin_amdgcn_s_setprio(1);
-      store_own<M>(SH, sstride, 0, nv, piece0, npieces, wave_s, lane, [&]() __attribute__((always_inline)) {
+      store_own<Rows<M>>(SH, sstride, 0, nv, piece0, npieces, wave_s, lane, [&]() __attribute__((always_inline)) {
         if (tid0 == 0) *slot = taken;
       });
       __builtin_amdgcn_s_setprio(0);
@@ -554,7 +313,7 @@ __global__ void __launch_bounds__(THREADS, 4) encode_kw(const uint8_t *__restric
     if constexpr (M == 8) {
       ipass<3>(s, baseB);
       xchg<LB, LC>(s, xb);
-      ipassC8(s);
+      ipassC(s);
     } else if constexpr (M == 7) {
       ipass<3>(s, baseB);
       xchg<LB, LC>(s, xb);
@@ -579,7 +338,7 @@ __global__ void __launch_bounds__(THREADS, 4) encode_kw(const uint8_t *__restric
 #pragma unroll
       for (int r = 0; r < 8; ++r) asm volatile("" : "+v"(coef.l[0][r]), "+v"(coef.h[0][r]));
       if constexpr (M == 8) {
-        fpassC8(s, coef, off);
+        fpassC(s, coef, off);
         // previous coset's rows read out; from coset 4 on, also this coset's
         // extension image landed in every wave (issued before the previous
         // coset's store phase: 4 stores per lane after it on the fast path)
@@ -656,22 +415,8 @@ template <int M>
 static hipError_t launch_m(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads, size_t plen,
                            size_t pstride, size_t batch, uint8_t *d_shards, size_t sstride, void *scratch,
                            hipStream_t s) {
-  int cus = 0;
-  if (const hipError_t e = prepare_kernel(reinterpret_cast<const void *>(&encode_kw<M>), lds_bytes<M>(), &cus);
-      e != hipSuccess)
-    return e;
-  const size_t sl = shard_len(p.k, plen);
-  const size_t tiles = (sl / 2 + Geo<M>::TILE - 1) / Geo<M>::TILE * batch;
-  if (tiles >= (size_t(1) << 32) - size_t(4) * cus) return hipErrorInvalidValue;
-  uint32_t *tick = static_cast<uint32_t *>(scratch);  // none: the static schedule
-  if (tick)
-    if (const hipError_t e = launch_zero_counters(tick, sizeof(uint32_t), s); e != hipSuccess) return e;
-  const size_t slots = 2 * size_t(cus);  // two workgroups per CU
-  const unsigned grid = unsigned(tiles < slots ? tiles : slots);
-  hipLaunchKernelGGL(encode_kw<M>, dim3(grid), dim3(THREADS), lds_bytes<M>(), s, d_payloads, uint64_t(plen),
-                     uint64_t(pstride), d_shards, uint64_t(sl), uint64_t(sstride), int(p.nv),
-                     uint32_t(batch), t.cimg, t.eimg256, tick);
-  return hipGetLastError();
+  return launch_w(encode_kw<M>, lds_bytes<M>(), Geo<M>::TILE, p, d_payloads, plen, pstride, batch, d_shards,
+                  sstride, scratch, s, t.cimg, t.eimg256);
 }
 
 hipError_t launch_encode_kw(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,

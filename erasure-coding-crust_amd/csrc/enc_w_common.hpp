@@ -1,0 +1,345 @@
+// enc_w_common.hpp — the one copy of what the two-workgroups-per-CU encode
+// kernels share (enc_k256w.hip, enc_kw.hip, enc_k512w.hip; DESIGN.md §5.1,
+// §5.7): 8-wave workgroups on the compact table image (cimg.hpp), radix-8
+// register passes in tower coordinates, wave-private LDS exchanges
+// (enc_k256_common.hpp), the payload fetch of a lane, the row stores out of
+// the waves' own regions and the launchers' tail.  Each kernel keeps its tile
+// loop, its idle-wave path, its coset sequencing, its LDS map and its staging
+// swizzle (soff*).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+
+#include "ec_device.hpp"
+#include "ec_kernels.hpp"
+#include "cimg.hpp"
+#include "enc_k256_common.hpp"
+
+namespace ecamd {
+namespace {
+
+constexpr int WAVES = 8;
+constexpr int THREADS = 64 * WAVES;
+constexpr uint32_t XCH_BYTES = 4096;  // per-wave exchange / staging region
+static_assert(kCImgBytes % (16 * THREADS) == 0, "whole image chunks per thread");
+
+// the compact image (32 KB) -> LDS address 0, every load issued before the
+// first store
+__device__ __forceinline__ void copy_cimg(uint8_t *lds, const uint8_t *cimg, uint32_t tid0) {
+  constexpr int kPer = int(kCImgBytes / 16 / THREADS);
+  v4u v[kPer];
+#pragma unroll
+  for (int k = 0; k < kPer; ++k) v[k] = reinterpret_cast<const v4u *>(cimg)[tid0 + k * THREADS];
+#pragma unroll
+  for (int k = 0; k < kPer; ++k) reinterpret_cast<v4u *>(lds)[tid0 + k * THREADS] = v[k];
+}
+
+// Element index of a stage-m butterfly whose a-position is pos, in a transform
+// at index off (a multiple of k): x = (pos + off) >> (m + 1) (ec_kernels.hpp).
+// A radix-8 pass over position bits b0..b0+2 held in registers (pos = base |
+// r << b0, base without those bits): stage b0 block rr (registers 2rr, 2rr+1)
+// x = base >> (b0+1) | rr; stage b0+1 block hh (registers 4hh + {0,1}, + 2)
+// x = base >> (b0+2) | hh; stage b0+2: x = base >> (b0+3); each | off >> (m+1).
+// Lane parts l0..l2 = cimg_lin of the three base shifts (3 VGPRs per pass).
+struct XLanes {
+  uint32_t l0, l1, l2;
+};
+template <int B0>
+__device__ __forceinline__ XLanes xlanes(uint32_t base) {
+  return {cimg_lin(base >> (B0 + 1)), cimg_lin(base >> (B0 + 2)), cimg_lin(base >> (B0 + 3))};
+}
+
+// inverse radix-8 pass at index 0 whose every element is subfield (x < 128)
+template <int B0>
+__device__ __forceinline__ void ipass(State &s, uint32_t base) {
+  const XLanes x = xlanes<B0>(base);
+  SubTab Ta0, Tb0, Ta1, Tb1, Ta2;
+  ctab(x.l0, cimg_lin(0), Ta0);
+  ctab(x.l0, cimg_lin(1), Tb0);
+  ibfly(s, 0, 1, Ta0);
+  ctab(x.l0, cimg_lin(2), Ta0);
+  ibfly(s, 2, 3, Tb0);
+  ctab(x.l0, cimg_lin(3), Tb0);
+  ibfly(s, 4, 5, Ta0);
+  ctab(x.l1, cimg_lin(0), Ta1);
+  ibfly(s, 6, 7, Tb0);
+  ctab(x.l1, cimg_lin(1), Tb1);
+  ibfly(s, 0, 2, Ta1);
+  ibfly(s, 1, 3, Ta1);
+  ctab(x.l2, cimg_lin(0), Ta2);
+  ibfly(s, 4, 6, Tb1);
+  ibfly(s, 5, 7, Tb1);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) ibfly(s, r, r + 4, Ta2);
+}
+
+// Table kinds of a stage: the compact image's subfield / F9 / general entries
+// (SubTab, F9Tab, Tab: the kind is the table type), or an extension kind of
+// the kernel: a struct derived from ExtKind whose BASE / PLANE give the LDS
+// address and plane pitch of a general table image brought in per coset.
+struct ExtKind {};
+template <typename K_>
+using TabOf = std::conditional_t<std::is_base_of_v<ExtKind, K_>, Tab, K_>;
+
+// table of element x = lane part lt ^ block part r ^ uniform part u (each the
+// cimg_lin of its bits): compact-image kinds at their element address, an
+// extension table at the coset-local one (u, the coset's offset bits, dropped)
+template <typename K_>
+__device__ __forceinline__ void ftab(uint32_t lt, uint32_t r, uint32_t u, TabOf<K_> &T) {
+  if constexpr (std::is_base_of_v<ExtKind, K_>) {
+    const uint32_t a = lt ^ r;
+#pragma unroll
+    for (int q = 4; q >= 0; --q) {
+      const v4u v = lds_r128(a + K_::BASE + uint32_t(q) * K_::PLANE);
+      T.t[4 * q] = v.x;
+      T.t[4 * q + 1] = v.y;
+      T.t[4 * q + 2] = v.z;
+      T.t[4 * q + 3] = v.w;
+    }
+  } else {
+    ctab(lt, r ^ u, T);
+  }
+}
+
+// forward radix-8 pass at index off over position bits B0..B0+2: stages B0+2,
+// B0+1, B0 with table kinds K2, K1, K0 (the elements' kinds, known per coset:
+// DESIGN.md §5.1).  u0..u2: the uniform parts (scalar for a run-time coset)
+template <int B0, typename K2, typename K1, typename K0>
+__device__ __forceinline__ void fpass(State &s, uint32_t base, uint32_t off) {
+  const XLanes x = xlanes<B0>(base);
+  const uint32_t u0 = cimg_lin(off >> (B0 + 1)), u1 = cimg_lin(off >> (B0 + 2)), u2 = cimg_lin(off >> (B0 + 3));
+  TabOf<K2> Ta2;
+  TabOf<K1> Ta1, Tb1;
+  TabOf<K0> Ta0, Tb0;
+  ftab<K2>(x.l2, 0u, u2, Ta2);
+  ftab<K1>(x.l1, 0u, u1, Tb1);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) fbfly(s, r, r + 4, Ta2);
+  ftab<K1>(x.l1, cimg_lin(1), u1, Ta1);
+  fbfly(s, 0, 2, Tb1);
+  fbfly(s, 1, 3, Tb1);
+  ftab<K0>(x.l0, 0u, u0, Tb0);
+  fbfly(s, 4, 6, Ta1);
+  fbfly(s, 5, 7, Ta1);
+  ftab<K0>(x.l0, cimg_lin(1), u0, Ta0);
+  fbfly(s, 0, 1, Tb0);
+  ftab<K0>(x.l0, cimg_lin(2), u0, Tb0);
+  fbfly(s, 2, 3, Ta0);
+  ftab<K0>(x.l0, cimg_lin(3), u0, Ta0);
+  fbfly(s, 4, 5, Tb0);
+  fbfly(s, 6, 7, Ta0);
+}
+
+// ---- layout C for k = 256 (register bit 0 = p6, bit 1 = p7, bit 2 = p5): the
+// elements of stages 6, 7 are lane-uniform.  IFFT at index 0: stage 7 (x = 0)
+// and stage 6's p7 = 0 block (x = 0) are b ^= a only (the skew 0xFFFF of
+// additive_fft.hpp:110-112); stage 6's p7 = 1 block has x = 1.
+__device__ __forceinline__ void ipassC(State &s) {
+  SubTab Tb;
+  ctab(0u, cimg_lin(1), Tb);
+  bxor(s, 0, 1);
+  bxor(s, 4, 5);
+  ibfly(s, 2, 3, Tb);
+  ibfly(s, 6, 7, Tb);
+  bxor(s, 0, 2);
+  bxor(s, 1, 3);
+  bxor(s, 4, 6);
+  bxor(s, 5, 7);
+}
+
+// FFT stages 7, 6 at index off, reading the IFFT coefficients c and writing s:
+// stage 7 x = off >> 8, stage 6 x = off >> 7 | p7
+__device__ __forceinline__ void fpassC(State &s, const State &c, uint32_t off) {
+  SubTab Ta, Tb;
+  ctab(0u, cimg_lin(off >> 8), Ta);
+  ctab(0u, cimg_lin(off >> 7), Tb);
+  fbfly_from(s, c, 0, 2, Ta);
+  fbfly_from(s, c, 1, 3, Ta);
+  fbfly_from(s, c, 4, 6, Ta);
+  fbfly_from(s, c, 5, 7, Ta);
+  ctab(0u, cimg_lin((off >> 7) | 1u), Ta);
+  fbfly(s, 0, 1, Tb);
+  fbfly(s, 4, 5, Tb);
+  fbfly(s, 2, 3, Ta);
+  fbfly(s, 6, 7, Ta);
+}
+
+// wave-private exchange (enc_k256_common.hpp exchange) at the wave's region
+// folded into the lane bases xb (bits >= 12): the bases are laundered here, so
+// the 16 cell addresses are formed at the exchange (one XOR each) instead of
+// being hoisted out of the tile loop and kept live (spilled) across it
+template <Layout FROM, Layout TO>
+__device__ __forceinline__ void xchg(State &s, XBase xb) {
+  asm volatile("" : "+v"(xb.a), "+v"(xb.b), "+v"(xb.c));
+#pragma unroll
+  for (int r = 0; r < 8; ++r) lds_st2(xcell<FROM>(xb, r), make_uint2(s.l[0][r], s.h[0][r]));
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    const uint2 v = lds_ld2(xcell<TO>(xb, r));
+    s.l[0][r] = v.x;
+    s.h[0][r] = v.y;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// ---- payload fetch: a lane's 4 x 16 payload bytes, zero past plen.  FP: the
+// payload; pw: the wave's first piece (uniform) of its wp; the lane takes
+// pieces pw + 4 g + u (g: its byte-planar group in the wave, u = 0..3), bytes
+// 16 q .. 16 q + 15 of each (2 K bytes a piece).  Whole wave inside the
+// payload: 4 loads in flight; the payload's edge: piece by piece, byte by byte
+// at plen; a wave past the end: zeros, no loads (every path assigns d: no
+// value is carried across a tile).
+template <int K>
+__device__ __forceinline__ void fetch_pieces(const uint8_t *FP, uint64_t plen, uint64_t npieces, uint64_t pw,
+                                             uint32_t wp, uint32_t g, uint32_t q, v4u (&d)[4]) {
+  if ((pw + wp) * 2 * K <= plen) {
+    const uint8_t *src = FP + (pw + 4 * g) * 2 * K + 16 * q;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) d[u] = *reinterpret_cast<const v4u *>(src + u * 2 * K);
+  } else if (pw < npieces) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const uint64_t off = (pw + 4 * g + u) * 2 * K + 16 * q;
+      uint32_t w[4] = {0, 0, 0, 0};
+      if (off + 16 <= plen) {
+        const v4u x = *reinterpret_cast<const v4u *>(FP + off);
+        w[0] = x.x;
+        w[1] = x.y;
+        w[2] = x.z;
+        w[3] = x.w;
+      } else {
+        for (uint64_t e = off; e < plen && e < off + 16; ++e)
+          w[(e - off) >> 2] |= uint32_t(FP[e]) << (8 * ((e - off) & 3));
+      }
+      d[u] = v4u{w[0], w[1], w[2], w[3]};
+    }
+  } else {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) d[u] = v4u{0, 0, 0, 0};
+  }
+}
+
+// 4 x 16 payload bytes (4 pieces, positions 8q..8q+7) -> byte-planar State:
+// 4x4 byte transposes, dword j of each piece = (hi_{2j}, lo_{2j}, hi_{2j+1}, lo_{2j+1})
+__device__ __forceinline__ void to_state(const v4u (&d)[4], State &s) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const uint32_t D0 = d[0][j], D1 = d[1][j], D2 = d[2][j], D3 = d[3][j];
+    const uint32_t t0 = vperm(D1, D0, 0x05010400u), t1 = vperm(D1, D0, 0x07030602u);
+    const uint32_t u0 = vperm(D3, D2, 0x05010400u), u1 = vperm(D3, D2, 0x07030602u);
+    s.h[0][2 * j] = vperm(u0, t0, 0x05040100u);
+    s.l[0][2 * j] = vperm(u0, t0, 0x07060302u);
+    s.h[0][2 * j + 1] = vperm(u1, t1, 0x05040100u);
+    s.l[0][2 * j + 1] = vperm(u1, t1, 0x07060302u);
+  }
+}
+
+// ---- row stores, all waves: rows [s0, s0 + K) of the tile from the 8 regions
+// -> shards, 16 B (pieces 8c .. 8c + 7 of one row) per lane and iteration, 4
+// iterations.  The kernel's geometry G gives
+//   TILE, K        pieces per tile, rows per store phase;
+//   VSTEP          rows per iteration (all waves): K / 4;
+//   lane_role(wave, lane)   the lane's first row v0, its chunk c and the LDS
+//                  address a of that row's chunk;
+//   read(a, it)    the 16 bytes of row v0 + it * VSTEP (the staging swizzles
+//                  are GF(2)-linear in v = it * VSTEP | v0: one XOR on a), as
+//                  a v4u or what converts to one (the slow path converts
+//                  only the rows it stores).
+// Fast path (uniform): 16-B aligned rows, the whole tile inside the payload,
+// all K rows below n_validators -- one streaming 16-B store per lane and row.
+struct RowLane {
+  uint32_t v0, c, a;
+};
+template <typename G>
+__device__ __forceinline__ bool store_fast(const uint8_t *SH, uint64_t sstride, uint32_t s0, int nv,
+                                           uint64_t piece0, uint64_t npieces) {
+  return ((sstride | reinterpret_cast<uintptr_t>(SH)) & 15) == 0 && piece0 + G::TILE <= npieces &&
+         int(s0) + int(G::K) <= nv;
+}
+
+// `then` runs at the end of each path: code that waits for a load issued
+// before the stores is placed there, so the compiler's wait on the fast path
+// counts its 4 stores (vmcnt(4)) instead of the minimum over every path.
+template <typename G, typename Then>
+__device__ __forceinline__ void store_own(uint8_t *SH, uint64_t sstride, uint32_t s0, int nv,
+                                          uint64_t piece0, uint64_t npieces, uint32_t wave,
+                                          uint32_t lane, Then &&then) {
+  static_assert(G::K == 4 * G::VSTEP, "4 stores per lane: the vmcnt(4) waits count them");
+  asm volatile("" : "+v"(lane));  // recomputed here, not kept live across the FFTs
+  const RowLane rl = G::lane_role(wave, lane);
+  const uint32_t v0 = rl.v0, c = rl.c, a = rl.a;
+  if (store_fast<G>(SH, sstride, s0, nv, piece0, npieces)) {
+    uint8_t *dst = SH + uint64_t(s0 + v0) * sstride + 2 * (piece0 + 8 * c);
+    const uint64_t dstep = uint64_t(G::VSTEP) * sstride;
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+      const v4u val = G::read(a, it);
+      __builtin_nontemporal_store(val, reinterpret_cast<v4u *>(dst + it * dstep));  // written once
+    }
+    then();
+    asm volatile("; store_own fast path end" ::: "memory");  // distinct tails: `then` is not merged
+    return;
+  }
+  const uint64_t p = piece0 + 8 * c;
+  const bool wide = ((sstride | reinterpret_cast<uintptr_t>(SH)) & 15) == 0;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const uint32_t v = uint32_t(it) * G::VSTEP + v0;
+    const auto raw = G::read(a, it);  // a v4u only below: not assembled for rows that are cut
+    const uint32_t shard = s0 + v;
+    if (int(shard) >= nv) continue;
+    uint8_t *dst = SH + uint64_t(shard) * sstride + 2 * p;
+    const v4u val = raw;
+    if (p + 8 <= npieces) {
+      if (wide) {
+        *reinterpret_cast<v4u *>(dst) = val;
+      } else {
+        reinterpret_cast<uint2 *>(dst)[0] = make_uint2(val.x, val.y);
+        reinterpret_cast<uint2 *>(dst)[1] = make_uint2(val.z, val.w);
+      }
+    } else if (p < npieces) {
+      const uint32_t w[4] = {val.x, val.y, val.z, val.w};
+      for (uint64_t e = 0; e < npieces - p; ++e)
+        *reinterpret_cast<uint16_t *>(dst + 2 * e) = uint16_t(w[e >> 1] >> (16 * (e & 1)));
+    }
+  }
+  then();
+  asm volatile("; store_own slow path end" ::: "memory");
+}
+
+}  // namespace
+
+// ---- the launchers' tail: the kernel prepared for its dynamic LDS, the tile
+// count (payload pieces in tiles of `tile`) below 2^32 - 4 CUs (the kernels
+// count tiles, and the static schedule's cur + gridDim.x, in 32 bits), the
+// tile counter (`scratch`: k256_scratch_bytes and its like) zeroed in stream
+// order, grid = min(tiles, two workgroups per CU).  No scratch: the static
+// schedule (a missing counter costs speed, not an error).  `tabs`: the
+// kernel's table images, passed between batch and the counter.
+template <typename Kern, typename... Tabs>
+hipError_t launch_w(Kern kern, int lds_bytes, size_t tile, const CodeParams &p, const uint8_t *d_payloads,
+                    size_t plen, size_t pstride, size_t batch, uint8_t *d_shards, size_t sstride,
+                    void *scratch, hipStream_t s, Tabs... tabs) {
+  int cus = 0;
+  if (const hipError_t e = prepare_kernel(reinterpret_cast<const void *>(kern), lds_bytes, &cus); e != hipSuccess)
+    return e;
+  const size_t sl = shard_len(p.k, plen);
+  const size_t tiles = (sl / 2 + tile - 1) / tile * batch;
+  if (tiles >= (size_t(1) << 32) - size_t(4) * cus) return hipErrorInvalidValue;
+  uint32_t *tick = static_cast<uint32_t *>(scratch);
+  if (tick)
+    if (const hipError_t e = launch_zero_counters(tick, sizeof(uint32_t), s); e != hipSuccess) return e;
+  const size_t slots = 2 * size_t(cus);
+  const unsigned grid = unsigned(tiles < slots ? tiles : slots);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), lds_bytes, s, d_payloads, uint64_t(plen),
+                     uint64_t(pstride), d_shards, uint64_t(sl), uint64_t(sstride), int(p.nv),
+                     uint32_t(batch), tabs..., tick);
+  return hipGetLastError();
+}
+
+}  // namespace ecamd

@@ -499,11 +499,5 @@ __device__ __forceinline__ void fft_restricted(S16 &s, const uint8_t *tabs, uint
   }
 }
 
-
-// byte-planar group (4 pieces / columns) -> big-endian u16 x4
-__device__ __forceinline__ uint2 to_be(uint32_t l, uint32_t h) {
-  return make_uint2(vperm(l, h, 0x05010400u), vperm(l, h, 0x07030602u));
-}
-
 }  // namespace tf
 }  // namespace ecamd

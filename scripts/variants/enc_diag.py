@@ -4,7 +4,11 @@ the headline encode.  Each removes one kind of work and
 keeps every instruction of the rest, so the kernel-time difference is what
 that work costs in the real interleaving:
 
-  enc_diag.py KIND OUTDIR   writes OUTDIR/enc_k256w.hip and OUTDIR/cimg.hpp
+  enc_diag.py KIND OUTDIR   writes OUTDIR/enc_k256w.hip, OUTDIR/enc_w_common.hpp
+                            (the payload fetch, the row stores and the launch
+                            tail that enc_k256w.hip shares with enc_kw.hip and
+                            enc_k512w.hip: those kernels change with it) and
+                            OUTDIR/cimg.hpp
     nobar   the per-tile workgroup barriers dropped (LDS races: garbage rows)
     static  tiles by a static grid stride instead of the ticket counter: with
             barriers dropped the tickets are read unsynchronised (lagging
@@ -41,7 +45,7 @@ that work costs in the real interleaving:
             s_memrealtime (100 MHz) over its lifetime: the clock under load
             (scripts/variants/clk_run.py); combine as e.g. clk+nostg
 
-Build: scripts/build_var.sh diag_KIND "" enc_k256w.hip=OUT/enc_k256w.hip cimg.hpp=OUT/cimg.hpp"""
+Build: scripts/build_var.sh diag_KIND "" enc_k256w.hip=OUT/enc_k256w.hip enc_w_common.hpp=OUT/enc_w_common.hpp cimg.hpp=OUT/cimg.hpp"""
 import os
 import sys
 
@@ -50,6 +54,7 @@ CS = f"{ROOT}/erasure-coding-crust_amd/csrc"
 kind, out = sys.argv[1], sys.argv[2]
 os.makedirs(out, exist_ok=True)
 enc = open(f"{CS}/enc_k256w.hip").read()
+com = open(f"{CS}/enc_w_common.hpp").read()
 cim = open(f"{CS}/cimg.hpp").read()
 dec = open(f"{CS}/dec_n1024.hip").read()
 decx = open(f"{CS}/dec_n1024x.hip").read()
@@ -105,11 +110,15 @@ for k in kinds:
                   "    if ((tid0 & 63) == 0) taken = atomicAdd(tick + 32 + 32 * (tid0 >> 6), 1u);")
         enc = rep(enc, "      next = __builtin_amdgcn_readfirstlane(*slot);", "      next = __builtin_amdgcn_readfirstlane(taken);")
         # one counter per wave index, each on its own 128-B line (8 on one
-        # line serialise in L2: ~6 ns per atomic); 1152 B of scratch
-        enc = rep(enc, "launch_zero_counters(tick, sizeof(uint32_t), s)", "launch_zero_counters(tick, 1152, s)")
+        # line serialise in L2: ~6 ns per atomic); 1152 B of scratch, zeroed by
+        # the shared launch tail: every kernel launched through it gets them
+        com = rep(com, "launch_zero_counters(tick, sizeof(uint32_t), s)", "launch_zero_counters(tick, 1152, s)")
         extra["enc_k256.hip"] = rep(open(f"{CS}/enc_k256.hip").read(),
                                     "size_t k256_scratch_bytes(const CodeParams &) { return 256; }",
                                     "size_t k256_scratch_bytes(const CodeParams &) { return 1152; }")
+        extra["enc_kw.hip"] = rep(open(f"{CS}/enc_kw.hip").read(), "kw_applicable(p) ? 256 : 0", "kw_applicable(p) ? 1152 : 0")
+        extra["enc_k512w.hip"] = rep(open(f"{CS}/enc_k512w.hip").read(), "k512w_applicable(p) ? 256 : 0",
+                                     "k512w_applicable(p) ? 1152 : 0")
     elif k == "nbread":
         for old in ("    rsync();  // the other waves are done reading this region (last tile)\n",
                     "    rsync();  // systematic rows read out of the regions\n",
@@ -124,13 +133,13 @@ for k in kinds:
                          ("        rsync();  // rows staged\n", "")):
             enc = rep(enc, old, new)
     elif k == "nost":
-        enc = rep(enc, "  asm volatile(\"\" : \"+v\"(lane));  // recomputed here, not kept live across the FFTs\n",
+        com = rep(com, "  asm volatile(\"\" : \"+v\"(lane));  // recomputed here, not kept live across the FFTs\n",
                   "  asm volatile(\"\" : \"+v\"(lane));\n  if (s0 != 0xFFFFFFFFu) {\n    then();\n    return;\n  }\n")
     elif k == "nostg":
-        enc = rep(enc, "      __builtin_nontemporal_store(val, reinterpret_cast<v4u *>(dst + it * dstep));  // written once\n",
+        com = rep(com, "      __builtin_nontemporal_store(val, reinterpret_cast<v4u *>(dst + it * dstep));  // written once\n",
                   "      asm volatile(\"\" :: \"v\"(val), \"v\"(dst + it * dstep));\n")
     elif k == "stplain":
-        enc = rep(enc, "      __builtin_nontemporal_store(val, reinterpret_cast<v4u *>(dst + it * dstep));  // written once\n",
+        com = rep(com, "      __builtin_nontemporal_store(val, reinterpret_cast<v4u *>(dst + it * dstep));  // written once\n",
                   "      *reinterpret_cast<v4u *>(dst + it * dstep) = val;\n")
     elif k == "noprio":
         enc = enc.replace("__builtin_amdgcn_s_setprio(1);", "").replace("__builtin_amdgcn_s_setprio(0);", "")
@@ -207,8 +216,8 @@ for k in kinds:
                   "    __builtin_amdgcn_s_setprio(0);  // the next tile's gather: equal\n  }\n" + CLK_END + "}\n")
         dec += READER
     elif k == "nold":
-        enc = rep(enc, "      for (int u = 0; u < 4; ++u) d[u] = *reinterpret_cast<const v4u *>(src + u * 2 * K);\n",
-                  "      for (int u = 0; u < 4; ++u) d[u] = v4u{uint32_t(pw) * 0x9E3779B1u + u, uint32_t(fb) ^ 0x5bd1e995u, q * 77u, inst};\n")
+        com = rep(com, "    for (int u = 0; u < 4; ++u) d[u] = *reinterpret_cast<const v4u *>(src + u * 2 * K);\n",
+                  "    for (int u = 0; u < 4; ++u) d[u] = v4u{uint32_t(pw) * 0x9E3779B1u + u, uint32_t(uintptr_t(FP)) ^ 0x5bd1e995u, q * 77u, g};\n")
     elif k == "notab":
         for typ, n in (("SubTab", 5), ("F9Tab", 16), ("Tab", 20)):
             start = cim.index(f"__device__ __forceinline__ void ctab(uint32_t lt, uint32_t u, {typ} &T) {{")
@@ -220,6 +229,7 @@ for k in kinds:
     else:
         raise SystemExit(f"unknown kind {k}")
 open(f"{out}/enc_k256w.hip", "w").write(enc)
+open(f"{out}/enc_w_common.hpp", "w").write(com)
 open(f"{out}/cimg.hpp", "w").write(cim)
 open(f"{out}/dec_n1024.hip", "w").write(dec)
 for fname, src in extra.items():

@@ -26,8 +26,8 @@ open(f"{out}/cimg.hpp", "w").write(c)
 k = open(f"{ROOT}/erasure-coding-crust_amd/csrc/enc_k256w.hip").read()
 k = rep(k, "constexpr int LDS_BYTES = int(SLOT + 16);", "constexpr int LDS_BYTES = int(SLOT + 16 + 512);\n"
         "static_assert(SLOT + 16 == kSub1Packed, \"packed plane after the slot\");")
-k = rep(k, "    for (int k = 0; k < kPer; ++k) reinterpret_cast<v4u *>(lds)[tid0 + k * THREADS] = v[k];\n",
-        "    for (int k = 0; k < kPer; ++k) reinterpret_cast<v4u *>(lds)[tid0 + k * THREADS] = v[k];\n"
-        "    if (tid0 < 128) reinterpret_cast<uint32_t *>(lds + kSub1Packed)[tid0] =\n"
-        "        reinterpret_cast<const uint32_t *>(cimg + kCImgSub1)[4 * tid0];\n")
+k = rep(k, "  copy_cimg(lds, cimg, tid0);\n",
+        "  copy_cimg(lds, cimg, tid0);\n"
+        "  if (tid0 < 128) reinterpret_cast<uint32_t *>(lds + kSub1Packed)[tid0] =\n"
+        "      reinterpret_cast<const uint32_t *>(cimg + kCImgSub1)[4 * tid0];\n")
 open(f"{out}/enc_k256w.hip", "w").write(k)

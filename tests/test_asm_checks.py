@@ -69,7 +69,7 @@ def test_enc_k1024_fast_store_count(tmp_path):
 
 
 def test_enc_k256w_fast_store_count(tmp_path):
-    # enc_k256w.hip: store_own8's fast path, 4 stores per lane; the compiler's
+    # enc_k256w.hip: store_own's fast path, 4 stores per lane; the compiler's
     # own vmcnt(4) before the next tile's transposes depends on it too
     blocks = _nt_store_blocks(_asm("enc_k256w.hip", tmp_path), "encode_k256w")
     assert blocks and all(c == 4 for c in blocks), blocks
