@@ -21,6 +21,7 @@
 #include "ec_kernels.hpp"
 #include "ec_runtime.hpp"
 #include "gf_field.hpp"
+#include "ragged.hpp"
 
 using namespace ecamd;
 
@@ -544,6 +545,116 @@ NPRSResult reconstruct_batch(unsigned long nv, const uint8_t *d_shards, unsigned
     return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
   return result(NPRS_RESULT_OK);
 }
+
+// ---- ragged device batches (ragged.hpp).  What the host can see is checked
+// here, before anything is launched and before the device is touched; the
+// items live on the device and are validated there (the plan kernel).
+static_assert(sizeof(ECCR_AMD_RaggedItem) == sizeof(RaggedItem) && sizeof(RaggedItem) == 40, "item layout");
+
+bool aligned16(const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+
+// batch and the stated maximum: a count the 32-bit item indices and tile
+// tickets can hold.  tiles_of_max: tiles of the longest item the call allows.
+NPRSResult ragged_counts(const char *what, unsigned long batch, unsigned long max_len, size_t tiles_of_max,
+                         NPRSResult_Tag empty_tag) {
+  if (batch == 0 || batch >= (1ul << 31)) {
+    set_error(std::string("erasure_coding_crust(amd): ") + what + ": batch " + std::to_string(batch) +
+              " is outside 1 .. 2^31 - 1");
+    return result(NPRS_RESULT_BAD_PAYLOAD);
+  }
+  if (max_len == 0) {
+    set_error(std::string("erasure_coding_crust(amd): ") + what + ": a maximum length of 0");
+    return result(empty_tag);
+  }
+  // batch * tiles(max) bounds every ticket; the kernels' grids add a few
+  // thousand tickets past the end
+  if (tiles_of_max >= (size_t(1) << 32) || size_t(batch) * tiles_of_max + 4096 >= (size_t(1) << 32)) {
+    set_error(std::string("erasure_coding_crust(amd): ") + what + ": batch x tiles of the maximum length (" +
+              std::to_string(batch) + " x " + std::to_string(tiles_of_max) + ") reaches 2^32");
+    return result(NPRS_RESULT_BAD_PAYLOAD);
+  }
+  return result(NPRS_RESULT_OK);
+}
+
+// a ragged call always needs its workspace (the plan lives in it): checked
+// without a device, nothing launched on failure
+bool ragged_workspace_ok(const Workspace &ws, size_t need) {
+  if (ws.ptr && ws.bytes >= need && reinterpret_cast<uintptr_t>(ws.ptr) % 256 == 0) return true;
+  set_error("erasure_coding_crust(amd): workspace of " + std::to_string(ws.bytes) +
+            " bytes (256-B aligned required) is below the " + std::to_string(need) +
+            " bytes this ragged call needs (ECCR_AMD_*_ragged_workspace_bytes)");
+  return false;
+}
+
+NPRSResult encode_ragged(unsigned long nv, const uint8_t *d_payloads, const ECCR_AMD_RaggedItem *d_items,
+                         unsigned long batch, unsigned long max_plen, uint8_t *d_shards, uint32_t *d_status,
+                         hipStream_t s, const Workspace *ws) {
+  CodeParams p;
+  NPRSResult r = params_or_error(nv, &p);
+  if (r.tag != NPRS_RESULT_OK) return r;
+  if (!d_payloads || !d_items || !d_shards) {
+    set_error("erasure_coding_crust(amd): encode_ragged: a NULL buffer");
+    return result(NPRS_RESULT_BAD_PAYLOAD);
+  }
+  const size_t tile = ragged_encode_tile(p);
+  r = ragged_counts("encode_ragged", batch, max_plen, (shard_len(p.k, max_plen) / 2 + tile - 1) / tile,
+                    NPRS_RESULT_BAD_PAYLOAD);
+  if (r.tag != NPRS_RESULT_OK) return r;
+  if (!aligned16(d_payloads) || !aligned16(d_shards) || reinterpret_cast<uintptr_t>(d_items) % 8 != 0 ||
+      reinterpret_cast<uintptr_t>(d_status) % 4 != 0) {
+    set_error("erasure_coding_crust(amd): encode_ragged: d_payloads and d_shards must be 16-B aligned, d_items 8-B");
+    return result(NPRS_RESULT_BAD_PAYLOAD);
+  }
+  const size_t need = ragged_encode_workspace_bytes(p, batch, max_plen);
+  if (ws && !ragged_workspace_ok(*ws, need)) return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
+  DeviceState *d = device_state();
+  if (!d) return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
+  BatchScratch sc(d, need, s, ws);
+  if (!sc.ok) return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
+  if (!hip_check(launch_encode_ragged(p, device_tables(d), d_payloads, reinterpret_cast<const RaggedItem *>(d_items),
+                                      batch, max_plen, d_shards, d_status, sc.p, s),
+                 "ragged encode launch"))
+    return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
+  return result(NPRS_RESULT_OK);
+}
+
+NPRSResult reconstruct_ragged(unsigned long nv, const uint8_t *d_shards, const ECCR_AMD_RaggedItem *d_items,
+                              const uint8_t *d_present, const uint16_t *d_err_log, const uint32_t *d_pattern,
+                              unsigned long batch, unsigned long max_slen, uint8_t *d_out, uint32_t *d_status,
+                              hipStream_t s, const Workspace *ws) {
+  CodeParams p;
+  NPRSResult r = params_or_error(nv, &p);
+  if (r.tag != NPRS_RESULT_OK) return r;
+  if (!d_shards || !d_items || !d_present || !d_err_log || !d_out) {
+    set_error("erasure_coding_crust(amd): reconstruct_ragged: a NULL buffer");
+    return result(NPRS_RESULT_BAD_PAYLOAD);
+  }
+  const size_t tile = ragged_reconstruct_tile(p);
+  r = ragged_counts("reconstruct_ragged", batch, max_slen, (max_slen / 2 + tile - 1) / tile,
+                    NPRS_RESULT_NON_UNIFORM_CHUNKS);
+  if (r.tag != NPRS_RESULT_OK) return r;
+  // (the n = 1024 kernel reads a pattern's flag and locator rows with vector loads)
+  if (!aligned16(d_shards) || !aligned16(d_out) || !aligned16(d_present) || !aligned16(d_err_log) ||
+      reinterpret_cast<uintptr_t>(d_items) % 8 != 0 || reinterpret_cast<uintptr_t>(d_pattern) % 4 != 0 ||
+      reinterpret_cast<uintptr_t>(d_status) % 4 != 0) {
+    set_error(
+        "erasure_coding_crust(amd): reconstruct_ragged: d_shards, d_out, d_present and d_err_log must be 16-B "
+        "aligned, d_items 8-B");
+    return result(NPRS_RESULT_BAD_PAYLOAD);
+  }
+  const size_t need = ragged_reconstruct_workspace_bytes(p, batch, max_slen);
+  if (ws && !ragged_workspace_ok(*ws, need)) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
+  DeviceState *d = device_state();
+  if (!d) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
+  BatchScratch sc(d, need, s, ws);
+  if (!sc.ok) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
+  if (!hip_check(launch_reconstruct_ragged(p, device_tables(d), d_shards, reinterpret_cast<const RaggedItem *>(d_items),
+                                           d_present, d_err_log, d_pattern, batch, max_slen, d_out, d_status, sc.p,
+                                           s),
+                 "ragged reconstruct launch"))
+    return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
+  return result(NPRS_RESULT_OK);
+}
 }  // namespace
 
 extern "C" {
@@ -703,6 +814,78 @@ NPRSResult ECCR_AMD_systematic_batch(unsigned long nv, const uint8_t *d_shards, 
                  "systematic launch"))
     return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
   return result(NPRS_RESULT_OK);
+}
+
+NPRSResult ECCR_AMD_encode_ragged(unsigned long nv, const uint8_t *d_payloads,
+                                  const ECCR_AMD_RaggedItem *d_items, unsigned long batch,
+                                  unsigned long max_plen, uint8_t *d_shards, uint32_t *d_status, void *stream) {
+  return encode_ragged(nv, d_payloads, d_items, batch, max_plen, d_shards, d_status,
+                       static_cast<hipStream_t>(stream), nullptr);
+}
+
+NPRSResult ECCR_AMD_encode_ragged_ws(unsigned long nv, const uint8_t *d_payloads,
+                                     const ECCR_AMD_RaggedItem *d_items, unsigned long batch,
+                                     unsigned long max_plen, uint8_t *d_shards, uint32_t *d_status,
+                                     void *d_workspace, unsigned long workspace_bytes, void *stream) {
+  const Workspace ws{d_workspace, workspace_bytes};
+  return encode_ragged(nv, d_payloads, d_items, batch, max_plen, d_shards, d_status,
+                       static_cast<hipStream_t>(stream), &ws);
+}
+
+NPRSResult ECCR_AMD_reconstruct_ragged(unsigned long nv, const uint8_t *d_shards,
+                                       const ECCR_AMD_RaggedItem *d_items, const uint8_t *d_present,
+                                       const uint16_t *d_err_log, const uint32_t *d_pattern,
+                                       unsigned long batch, unsigned long max_slen, uint8_t *d_out,
+                                       uint32_t *d_status, void *stream) {
+  return reconstruct_ragged(nv, d_shards, d_items, d_present, d_err_log, d_pattern, batch, max_slen, d_out,
+                            d_status, static_cast<hipStream_t>(stream), nullptr);
+}
+
+NPRSResult ECCR_AMD_reconstruct_ragged_ws(unsigned long nv, const uint8_t *d_shards,
+                                          const ECCR_AMD_RaggedItem *d_items, const uint8_t *d_present,
+                                          const uint16_t *d_err_log, const uint32_t *d_pattern,
+                                          unsigned long batch, unsigned long max_slen, uint8_t *d_out,
+                                          uint32_t *d_status, void *d_workspace,
+                                          unsigned long workspace_bytes, void *stream) {
+  const Workspace ws{d_workspace, workspace_bytes};
+  return reconstruct_ragged(nv, d_shards, d_items, d_present, d_err_log, d_pattern, batch, max_slen, d_out,
+                            d_status, static_cast<hipStream_t>(stream), &ws);
+}
+
+unsigned long ECCR_AMD_encode_ragged_workspace_bytes(unsigned long nv, unsigned long batch,
+                                                     unsigned long max_plen) {
+  CodeParams p;
+  if (code_params(nv, &p) != ParamError::kOk || batch == 0 || batch >= (1ul << 31) || max_plen == 0) return 0;
+  return ragged_encode_workspace_bytes(p, batch, max_plen);
+}
+
+unsigned long ECCR_AMD_reconstruct_ragged_workspace_bytes(unsigned long nv, unsigned long batch,
+                                                          unsigned long max_slen) {
+  CodeParams p;
+  if (code_params(nv, &p) != ParamError::kOk || batch == 0 || batch >= (1ul << 31) || max_slen == 0) return 0;
+  return ragged_reconstruct_workspace_bytes(p, batch, max_slen);
+}
+
+NPRSResult ECCR_AMD_ragged_check(unsigned long nv, const ECCR_AMD_RaggedItem *h_items, unsigned long batch,
+                                 unsigned long max_len, int reconstruct, uint32_t status[2]) {
+  CodeParams p;
+  NPRSResult r = params_or_error(nv, &p);
+  if (r.tag != NPRS_RESULT_OK) return r;
+  if (!h_items || !status || batch == 0 || batch >= (1ul << 31)) return result(NPRS_RESULT_BAD_PAYLOAD);
+  ragged_check_host(p, reinterpret_cast<const RaggedItem *>(h_items), batch, max_len, reconstruct != 0, status);
+  return result(NPRS_RESULT_OK);
+}
+
+const char *ECCR_AMD_encode_ragged_kernel(unsigned long nv) {
+  CodeParams p;
+  if (code_params(nv, &p) != ParamError::kOk) return nullptr;
+  return ragged_kernel_name(choose_encode_ragged(p));
+}
+
+const char *ECCR_AMD_reconstruct_ragged_kernel(unsigned long nv) {
+  CodeParams p;
+  if (code_params(nv, &p) != ParamError::kOk) return nullptr;
+  return ragged_kernel_name(choose_reconstruct_ragged(p));
 }
 
 void ECCR_AMD_set_scratch_limit(unsigned long bytes) { set_scratch_limit(bytes); }

@@ -12,6 +12,7 @@
 
 #include "ec_device.hpp"
 #include "ec_kernels.hpp"
+#include "ragged.hpp"
 
 namespace ecamd {
 namespace {
@@ -143,72 +144,98 @@ __device__ __forceinline__ void signal_end(uint32_t *flag, uint32_t v) {
   if (threadIdx.x == 0) __hip_atomic_store(flag, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// reed-solomon.hpp:47-81 + poly_encoder.hpp:31-86,217-240 for 4*G pieces
+// ---- geometry policies of the generic kernels: where item b's payload,
+// shard rows and output are and how long they are, for the block's tile
+// blockIdx.x (4 G pieces / positions).  `on` false: the block has nothing to
+// do for that item (block-uniform; tested before any barrier of the iteration).
+// The reconstruct's policies answer field by field (on, rows, outp, npos,
+// pitch), in the order the kernel body asks.
+struct EncItemG {
+  const uint8_t *P;
+  uint8_t *SH;
+  uint64_t plen, npieces, sstride;
+  bool on;
+};
+// the uniform batch: item b at b * pitch, every item as long as the others
+struct UniformEncG {
+  uint64_t plen, pstride, slen, sstride;
+  struct Pre {
+    uint64_t npieces;  // per launch: pieces per payload
+  };
+  __device__ __forceinline__ Pre prepare() const { return {slen / 2}; }
+  __device__ __forceinline__ EncItemG item(const Pre &p, const uint8_t *payloads, uint8_t *shards, uint32_t b,
+                                           int nv) const {
+    return {payloads + uint64_t(b) * pstride, shards + uint64_t(b) * nv * sstride, plen, p.npieces, sstride, true};
+  }
+};
+struct UniformRecG {
+  uint64_t slen, sstride, ostride;
+  struct Pre {
+    uint64_t npos;  // per launch: positions per shard
+  };
+  __device__ __forceinline__ Pre prepare() const { return {slen / 2}; }
+  __device__ __forceinline__ bool on(uint32_t) const { return true; }
+  __device__ __forceinline__ const uint8_t *rows(const uint8_t *shards, uint32_t b, int nv) const {
+    return shards + uint64_t(b) * nv * sstride;
+  }
+  __device__ __forceinline__ uint8_t *outp(uint8_t *out, uint32_t b) const { return out + uint64_t(b) * ostride; }
+  __device__ __forceinline__ uint64_t npos(const Pre &p, uint32_t) const { return p.npos; }
+  __device__ __forceinline__ uint64_t pitch(uint32_t) const { return sstride; }
+};
+struct NoPre {};
+// the ragged batch (ragged.hpp): item b's record, and its tile count from the
+// plan kernel's prefix; a block whose tile is past the item's last (or an item
+// without tiles: one that broke the contract) skips it without reading its record
+struct RaggedEncG {
+  const RaggedItem *items;
+  const uint32_t *tile_first;
+  int logk;
+  __device__ __forceinline__ NoPre prepare() const { return {}; }
+  __device__ __forceinline__ EncItemG item(NoPre, const uint8_t *payloads, uint8_t *shards, uint32_t b, int) const {
+    if (blockIdx.x >= tile_first[b + 1] - tile_first[b]) return {nullptr, nullptr, 0, 0, 0, false};
+    const RaggedItem it = items[b];
+    const uint64_t syms = it.payload_len / 2 + (it.payload_len & 1);
+    return {payloads + it.payload_off, shards + it.shard_off, it.payload_len,
+            (syms + (uint64_t(1) << logk) - 1) >> logk, it.shard_stride, true};
+  }
+};
+struct RaggedRecG {
+  const RaggedItem *items;
+  const uint32_t *tile_first;
+  __device__ __forceinline__ NoPre prepare() const { return {}; }
+  __device__ __forceinline__ bool on(uint32_t b) const { return blockIdx.x < tile_first[b + 1] - tile_first[b]; }
+  __device__ __forceinline__ const uint8_t *rows(const uint8_t *shards, uint32_t b, int) const {
+    return shards + items[b].shard_off;
+  }
+  __device__ __forceinline__ uint8_t *outp(uint8_t *out, uint32_t b) const { return out + items[b].payload_off; }
+  __device__ __forceinline__ uint64_t npos(NoPre, uint32_t b) const { return items[b].shard_len / 2; }
+  __device__ __forceinline__ uint64_t pitch(uint32_t b) const { return items[b].shard_stride; }
+};
+
+// reed-solomon.hpp:47-81 + poly_encoder.hpp:31-86,217-240 for 4*G pieces: the
+// body is enc_g_body.inc (one copy, shared with the ragged form)
 __global__ void __launch_bounds__(kBlock) encode_g(const uint8_t *__restrict__ payloads,
                                                    uint64_t plen, uint64_t pstride,
                                                    uint8_t *__restrict__ shards, uint64_t slen,
                                                    uint64_t sstride, int nv, int logn, int logk,
                                                    int logG, uint32_t batch, DevTables t,
                                                    uint2 *scratch, uint32_t *sig_flag, uint32_t sig_v) {
-  extern __shared__ __attribute__((aligned(16))) uint2 smem[];
-  const int k = 1 << logk, n = 1 << logn, G = 1 << logG;
-  const uint64_t npieces = slen / 2;
-  const uint64_t piece0 = uint64_t(blockIdx.x) * 4 * G;
-  uint2 *S = smem, *Cf = smem + size_t(k) * G;
-  if (scratch) {  // one buffer per block, reused by its payloads in turn
-    S = scratch + (uint64_t(blockIdx.y) * gridDim.x + blockIdx.x) * 2 * uint64_t(k) * G;
-    Cf = S + size_t(k) * G;
-  }
-  for (uint32_t b = blockIdx.y; b < batch; b += gridDim.y) {  // batch may exceed gridDim.y's limit
-  const uint8_t *P = payloads + uint64_t(b) * pstride;
-  uint8_t *SH = shards + uint64_t(b) * nv * sstride;
-  // BE-unpack 4 pieces per group, zero-padded (poly_encoder.hpp:53-76); the
-  // systematic shards are the data symbols themselves (poly_encoder.hpp:239)
-  for (int e = threadIdx.x; e < k * G; e += blockDim.x) {
-    const int g = e & (G - 1), i = e >> logG;
-    uint32_t xl = 0, xh = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const uint64_t p = piece0 + 4 * g + q;
-      const uint64_t off = p * 2 * uint64_t(k) + 2 * uint64_t(i);
-      const uint32_t hi = off < plen ? P[off] : 0;
-      const uint32_t lo = off + 1 < plen ? P[off + 1] : 0;
-      xl |= lo << (8 * q);
-      xh |= hi << (8 * q);
-      if (p < npieces) {
-        SH[uint64_t(i) * sstride + 2 * p] = uint8_t(hi);
-        SH[uint64_t(i) * sstride + 2 * p + 1] = uint8_t(lo);
-      }
-    }
-    S[e] = make_uint2(xl, xh);
-  }
-  __syncthreads();
-  ifft_g(S, logG, logk, 0, t);
-  for (int e = threadIdx.x; e < k * G; e += blockDim.x) Cf[e] = S[e];
-  __syncthreads();
-  for (int s = k; s < n && s < nv; s += k) {
-    if (s > k) {
-      for (int e = threadIdx.x; e < k * G; e += blockDim.x) S[e] = Cf[e];
-      __syncthreads();
-    }
-    fft_g(S, logG, logk, uint32_t(s), t);
-    for (int e = threadIdx.x; e < k * G; e += blockDim.x) {
-      const int g = e & (G - 1), v = s + (e >> logG);
-      if (v >= nv) continue;
-      const uint2 x = S[e];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const uint64_t p = piece0 + 4 * g + q;
-        if (p < npieces) {
-          SH[uint64_t(v) * sstride + 2 * p] = uint8_t(x.y >> (8 * q));
-          SH[uint64_t(v) * sstride + 2 * p + 1] = uint8_t(x.x >> (8 * q));
-        }
-      }
-    }
-    __syncthreads();
-  }
-  }
-  signal_end(sig_flag, sig_v);  // (single-workgroup launches only)
+  const UniformEncG geo{plen, pstride, slen, sstride};
+#include "enc_g_body.inc"
+}
+
+// the ragged form: grid.x from the longest item the call allows, the
+// blockIdx.y loop over the items
+__global__ void __launch_bounds__(kBlock) encode_g_ragged(const uint8_t *__restrict__ payloads,
+                                                          const RaggedItem *__restrict__ items,
+                                                          const uint32_t *__restrict__ tile_first,
+                                                          uint8_t *__restrict__ shards, int nv, int logn,
+                                                          int logk, int logG, uint32_t batch, DevTables t,
+                                                          uint2 *scratch) {
+  const RaggedEncG geo{items, tile_first, logk};
+  uint32_t *const sig_flag = nullptr;  // (no fused completion signal: never a per-call launch)
+  const uint32_t sig_v = 0;
+#include "enc_g_body.inc"
 }
 
 // poly_encoder.hpp:90-116 in the folded n-point form: one
@@ -405,89 +432,17 @@ __global__ void __launch_bounds__(kBlock) reconstruct_g(
     const uint8_t *__restrict__ present, const uint16_t *__restrict__ elog,
     uint8_t *__restrict__ out, uint64_t ostride, int nv, int logn, int logk, int logG,
     uint32_t batch, const uint32_t *__restrict__ pattern, DevTables t, uint2 *scratch) {
-  extern __shared__ __attribute__((aligned(16))) uint2 smem[];
-  const int n = 1 << logn, k = 1 << logk, G = 1 << logG;
-  const uint64_t npos = slen / 2;
-  const uint64_t pos0 = uint64_t(blockIdx.x) * 4 * G;
-  uint2 *S = smem, *D = smem + size_t(n) * G;
-  if (scratch) {  // one buffer per block, reused by its payloads in turn
-    S = scratch + (uint64_t(blockIdx.y) * gridDim.x + blockIdx.x) * 2 * uint64_t(n) * G;
-    D = S + size_t(n) * G;
-  }
-  for (uint32_t b = blockIdx.y; b < batch; b += gridDim.y) {  // batch may exceed gridDim.y's limit
-  const uint64_t pt = pattern ? pattern[b] : b;  // erasure pattern of payload b
-  const uint8_t *SH = shards + uint64_t(b) * nv * sstride;
-  const uint8_t *pr = present + pt * n;
-  const uint16_t *E = elog + pt * n;
-  uint8_t *O = out + uint64_t(b) * ostride;
-  __syncthreads();  // the previous payload's readers of S / D are done
-  // gather the column, multiply present symbols by the locator (decode_main:174-177)
-  for (int e = threadIdx.x; e < n * G; e += blockDim.x) {
-    const int g = e & (G - 1), v = e >> logG;
-    uint32_t yl = 0, yh = 0;
-    if (v < nv && pr[v]) {
-      uint32_t xl = 0, xh = 0;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const uint64_t pos = pos0 + 4 * g + q;
-        if (pos < npos) {
-          xh |= uint32_t(SH[uint64_t(v) * sstride + 2 * pos]) << (8 * q);
-          xl |= uint32_t(SH[uint64_t(v) * sstride + 2 * pos + 1]) << (8 * q);
-        }
-      }
-      Tab T;
-      load_tab(t.mtab, mul_index(E[v]), T);
-      mul_acc(xl, xh, T, yl, yh);
-    }
-    S[e] = make_uint2(yl, yh);
-  }
-  __syncthreads();
-  ifft_g(S, logG, logn, 0, t);
-  // formal derivative (poly_encoder.hpp:195-215), closed form:
-  //   c'[j] = c[j] ^ XOR_{b : bit b of j is 0} c[j | 2^b]
-  for (int e = threadIdx.x; e < n * G; e += blockDim.x) {
-    const int g = e & (G - 1), j = e >> logG;
-    uint2 acc = S[e];
-    for (int b = 0; b < logn; ++b)
-      if (!(j & (1 << b))) {
-        const uint2 o = S[(j | (1 << b)) * G + g];
-        acc.x ^= o.x;
-        acc.y ^= o.y;
-      }
-    D[e] = acc;
-  }
-  __syncthreads();
-  fft_g(D, logG, logn, 0, t);
-  // erased systematic positions: * locator (decode_main:185-188); present: as received
-  for (int e = threadIdx.x; e < k * G; e += blockDim.x) {
-    const int g = e & (G - 1), y = e >> logG;
-    const bool have = y < nv && pr[y];
-    uint32_t xl = 0, xh = 0;
-    if (have) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const uint64_t pos = pos0 + 4 * g + q;
-        if (pos < npos) {
-          xh |= uint32_t(SH[uint64_t(y) * sstride + 2 * pos]) << (8 * q);
-          xl |= uint32_t(SH[uint64_t(y) * sstride + 2 * pos + 1]) << (8 * q);
-        }
-      }
-    } else {
-      Tab T;
-      load_tab(t.mtab, mul_index(E[y]), T);
-      const uint2 r = D[e];
-      mul_acc(r.x, r.y, T, xl, xh);
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const uint64_t pos = pos0 + 4 * g + q;
-      if (pos < npos) {
-        O[(pos * k + y) * 2] = uint8_t(xh >> (8 * q));
-        O[(pos * k + y) * 2 + 1] = uint8_t(xl >> (8 * q));
-      }
-    }
-  }
-  }
+  const UniformRecG geo{slen, sstride, ostride};
+#include "dec_g_body.inc"
+}
+
+__global__ void __launch_bounds__(kBlock) reconstruct_g_ragged(
+    const uint8_t *__restrict__ shards, const RaggedItem *__restrict__ items,
+    const uint32_t *__restrict__ tile_first, const uint8_t *__restrict__ present,
+    const uint16_t *__restrict__ elog, uint8_t *__restrict__ out, int nv, int logn, int logk, int logG,
+    uint32_t batch, const uint32_t *__restrict__ pattern, DevTables t, uint2 *scratch) {
+  const RaggedRecG geo{items, tile_first};
+#include "dec_g_body.inc"
 }
 
 // reed-solomon.hpp:143-179: out[2(i*k + y) ..] = shard_y[2i ..]
@@ -819,6 +774,60 @@ hipError_t launch_systematic(const CodeParams &p, const uint8_t *d_shards, size_
   hipLaunchKernelGGL(systematic_g, dim3(unsigned(blocks), unsigned(grid_y(batch))), dim3(kBlock), 0,
                      s, d_shards, uint64_t(slen), uint64_t(sstride), int(p.nv), ilog2(p.k), d_out,
                      uint64_t(ostride), uint32_t(batch), fuse ? sig->flag : nullptr, fuse ? sig->v : 0u);
+  return hipGetLastError();
+}
+
+// ---- ragged forms of the generic kernels (ragged.hpp): the correctness path
+// of the ragged calls for every n_validators without a specialised ragged
+// kernel.  Tile = the block's 4 G pieces / positions; grid.x = the tiles of
+// the longest item the call allows; scratch (FFTs that do not fit LDS) one
+// buffer per block as in the uniform launch, sized from that maximum.
+uint32_t ragged_encode_tile(const CodeParams &p) {
+  return choose_encode_ragged(p) == RaggedKernel::encode_k256w_ragged ? 64u : 4u * uint32_t(groups_for(p.k));
+}
+uint32_t ragged_reconstruct_tile(const CodeParams &p) {
+  return choose_reconstruct_ragged(p) == RaggedKernel::reconstruct_n1024x_ragged ? 64u
+                                                                                 : 4u * uint32_t(groups_for(p.n));
+}
+
+size_t ragged_encode_g_scratch_bytes(const CodeParams &p, size_t batch, size_t max_plen) {
+  if (p.k <= uint32_t(kLdsSlots)) return 0;
+  const size_t tiles = (shard_len(p.k, max_plen) / 2 + 3) / 4;
+  return tiles * grid_y(batch) * 2 * size_t(p.k) * sizeof(uint2);
+}
+
+size_t ragged_reconstruct_g_scratch_bytes(const CodeParams &p, size_t batch, size_t max_slen) {
+  if (p.n <= uint32_t(kLdsSlots)) return 0;
+  const size_t tiles = (max_slen / 2 + 3) / 4;
+  return tiles * grid_y(batch) * 2 * size_t(p.n) * sizeof(uint2);
+}
+
+hipError_t launch_encode_g_ragged(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,
+                                  const RaggedItem *d_items, size_t batch, size_t max_plen, uint8_t *d_shards,
+                                  void *ws, hipStream_t s) {
+  const int G = groups_for(p.k);
+  const size_t tiles = (shard_len(p.k, max_plen) / 2 + 4 * G - 1) / (4 * G);
+  const bool lds = p.k <= uint32_t(kLdsSlots);
+  const size_t shm = lds ? 2 * size_t(p.k) * G * sizeof(uint2) : 0;
+  uint2 *scratch = reinterpret_cast<uint2 *>(static_cast<uint8_t *>(ws) + ragged_scratch_offset(batch));
+  hipLaunchKernelGGL(encode_g_ragged, dim3(unsigned(tiles), unsigned(grid_y(batch))), dim3(kBlock), shm, s,
+                     d_payloads, d_items, ragged_first(ws), d_shards, int(p.nv), ilog2(p.n), ilog2(p.k),
+                     ilog2(uint32_t(G)), uint32_t(batch), t, lds ? nullptr : scratch);
+  return hipGetLastError();
+}
+
+hipError_t launch_reconstruct_g_ragged(const CodeParams &p, const DevTables &t, const uint8_t *d_shards,
+                                       const RaggedItem *d_items, const uint8_t *d_present,
+                                       const uint16_t *d_err_log, const uint32_t *d_pattern, size_t batch,
+                                       size_t max_slen, uint8_t *d_out, void *ws, hipStream_t s) {
+  const int G = groups_for(p.n);
+  const size_t tiles = (max_slen / 2 + 4 * G - 1) / (4 * G);
+  const bool lds = p.n <= uint32_t(kLdsSlots);
+  const size_t shm = lds ? 2 * size_t(p.n) * G * sizeof(uint2) : 0;
+  uint2 *scratch = reinterpret_cast<uint2 *>(static_cast<uint8_t *>(ws) + ragged_scratch_offset(batch));
+  hipLaunchKernelGGL(reconstruct_g_ragged, dim3(unsigned(tiles), unsigned(grid_y(batch))), dim3(kBlock), shm, s,
+                     d_shards, d_items, ragged_first(ws), d_present, d_err_log, d_out, int(p.nv), ilog2(p.n),
+                     ilog2(p.k), ilog2(uint32_t(G)), uint32_t(batch), d_pattern, t, lds ? nullptr : scratch);
   return hipGetLastError();
 }
 

@@ -132,6 +132,16 @@ def lib():
             "ECCR_AMD_error_locator_ws": (NPRSResult, [ul, vp, ul, vp, vp, ul, vp]),
             "ECCR_AMD_reconstruct_batch_ws": (NPRSResult, [ul, vp, ul, ul, vp, vp, vp, ul, vp, ul,
                                                            vp, ul, vp]),
+            "ECCR_AMD_encode_ragged": (NPRSResult, [ul, vp, vp, ul, ul, vp, vp, vp]),
+            "ECCR_AMD_encode_ragged_ws": (NPRSResult, [ul, vp, vp, ul, ul, vp, vp, vp, ul, vp]),
+            "ECCR_AMD_reconstruct_ragged": (NPRSResult, [ul, vp, vp, vp, vp, vp, ul, ul, vp, vp, vp]),
+            "ECCR_AMD_reconstruct_ragged_ws": (NPRSResult, [ul, vp, vp, vp, vp, vp, ul, ul, vp, vp, vp,
+                                                            ul, vp]),
+            "ECCR_AMD_encode_ragged_workspace_bytes": (ul, [ul, ul, ul]),
+            "ECCR_AMD_reconstruct_ragged_workspace_bytes": (ul, [ul, ul, ul]),
+            "ECCR_AMD_ragged_check": (NPRSResult, [ul, vp, ul, ul, C.c_int, C.POINTER(C.c_uint32 * 2)]),
+            "ECCR_AMD_encode_ragged_kernel": (C.c_char_p, [ul]),
+            "ECCR_AMD_reconstruct_ragged_kernel": (C.c_char_p, [ul]),
             "ECCR_AMD_host_alloc": (vp, [ul]),
             "ECCR_AMD_host_free": (None, [vp]),
             "ECCR_AMD_encode_host_batch": (NPRSResult, [ul, vp, ul, ul, ul, vp, ul, ul]),
@@ -398,6 +408,107 @@ def systematic_batch(nv, d_shards, shard_len_, shard_stride, batch, d_out, out_s
     _check(lib().ECCR_AMD_systematic_batch(nv, _p(d_shards), shard_len_, shard_stride, batch,
                                            _p(d_out), out_stride, _stream(stream)),
            "systematic_batch")
+
+
+# ------------------------------------------------- ragged batches (ec_amd.h)
+
+
+class RaggedItem(C.Structure):  # ECCR_AMD_RaggedItem, 40 bytes
+    _fields_ = [("payload_off", C.c_uint64), ("payload_len", C.c_uint64), ("shard_off", C.c_uint64),
+                ("shard_len", C.c_uint64), ("shard_stride", C.c_uint64)]
+
+
+RAGGED_FIELDS = tuple(f for f, _ in RaggedItem._fields_)
+
+
+def _round16(x: int) -> int:
+    return (x + 15) // 16 * 16
+
+
+def ragged_items(nv: int, payload_lens, shard_pad=0):
+    """An item array for payloads of these lengths, laid out back to back: numpy uint64
+    [len(payload_lens)][5] (the fields of ECCR_AMD_RaggedItem in order; upload it as it is),
+    and the bytes of d_payloads, d_shards and d_out it spans.  Payload and shard regions
+    start at multiples of 16; shard_stride = the item's shard length rounded up to 16,
+    plus shard_pad (a multiple of 16; one value or one per item); payload_off doubles as
+    the reconstruct's output offset when payloads and outputs live in different buffers,
+    so consecutive payload regions are shard_len * k bytes apart (>= the payload)."""
+    import numpy as np
+    _, k, _ = code_params(nv)
+    lens = [int(x) for x in payload_lens]
+    pads = [int(shard_pad)] * len(lens) if isinstance(shard_pad, int) else [int(x) for x in shard_pad]
+    items = np.zeros((len(lens), 5), dtype=np.uint64)
+    poff = soff = 0
+    for i, (plen, pad) in enumerate(zip(lens, pads)):
+        sl = shard_len(nv, plen)
+        stride = _round16(sl) + pad
+        items[i] = (poff, plen, soff, sl, stride)
+        poff += _round16(sl * k)
+        soff += nv * stride
+    return items, poff, soff, poff
+
+
+def ragged_workspace_bytes(nv, batch, max_payload_len):
+    """(encode, reconstruct) device scratch bytes of a ragged batch of up to `batch` payloads
+    of up to max_payload_len bytes."""
+    L = lib()
+    return (int(L.ECCR_AMD_encode_ragged_workspace_bytes(nv, batch, max_payload_len)),
+            int(L.ECCR_AMD_reconstruct_ragged_workspace_bytes(nv, batch, shard_len(nv, max_payload_len))))
+
+
+def ragged_check(nv, items, max_len, reconstruct=False):
+    """(bad items, lowest bad index) of a host item array (numpy uint64 [batch][5] or a ctypes
+    array of RaggedItem): the device-side validation, run on the host."""
+    n = len(items)
+    status = (C.c_uint32 * 2)()
+    _check(lib().ECCR_AMD_ragged_check(nv, _p(items) if not isinstance(items, C.Array) else
+                                       C.cast(items, C.c_void_p), n, max_len, int(bool(reconstruct)),
+                                       C.byref(status)), "ragged_check")
+    return status[0], status[1]
+
+
+def _opt(x):
+    return None if x is None else _p(x)
+
+
+def encode_ragged(nv, d_payloads, d_items, batch, max_payload_len, d_shards, d_status=None, ws=None,
+                  stream=None):
+    """ECCR_AMD_encode_ragged, or its _ws form when a workspace tensor is given."""
+    if ws is None:
+        _check(lib().ECCR_AMD_encode_ragged(nv, _p(d_payloads), _p(d_items), batch, max_payload_len,
+                                            _p(d_shards), _opt(d_status), _stream(stream)),
+               "encode_ragged")
+        return
+    wp, wb = _ws(ws)
+    _check(lib().ECCR_AMD_encode_ragged_ws(nv, _p(d_payloads), _p(d_items), batch, max_payload_len,
+                                           _p(d_shards), _opt(d_status), wp, wb, _stream(stream)),
+           "encode_ragged_ws")
+
+
+def reconstruct_ragged(nv, d_shards, d_items, d_present, d_err_log, batch, max_shard_len, d_out,
+                       d_status=None, d_pattern=None, ws=None, stream=None):
+    """ECCR_AMD_reconstruct_ragged, or its _ws form when a workspace tensor is given."""
+    if ws is None:
+        _check(lib().ECCR_AMD_reconstruct_ragged(nv, _p(d_shards), _p(d_items), _p(d_present),
+                                                 _p(d_err_log), _opt(d_pattern), batch, max_shard_len,
+                                                 _p(d_out), _opt(d_status), _stream(stream)),
+               "reconstruct_ragged")
+        return
+    wp, wb = _ws(ws)
+    _check(lib().ECCR_AMD_reconstruct_ragged_ws(nv, _p(d_shards), _p(d_items), _p(d_present),
+                                                _p(d_err_log), _opt(d_pattern), batch, max_shard_len,
+                                                _p(d_out), _opt(d_status), wp, wb, _stream(stream)),
+           "reconstruct_ragged_ws")
+
+
+def encode_ragged_kernel(nv):
+    r = lib().ECCR_AMD_encode_ragged_kernel(nv)
+    return None if r is None else r.decode()
+
+
+def reconstruct_ragged_kernel(nv):
+    r = lib().ECCR_AMD_reconstruct_ragged_kernel(nv)
+    return None if r is None else r.decode()
 
 
 # --------------------------------------------------- host batches (ec_amd.h)

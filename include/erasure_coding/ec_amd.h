@@ -35,7 +35,8 @@
  *   reconstruct == ReedSolomon::reconstruct (include/ec-cpp/reed-solomon.hpp:83-134)
  *   systematic  == ReedSolomon::reconstruct_from_systematic (:143-179)
  *
- * Layouts (one batch = `batch` independent payloads of the same length):
+ * Layouts (one batch = `batch` independent payloads of the same length; for
+ * payloads of unequal length see "ragged batches" below):
  *   payloads   : [batch][payload_stride] bytes, payload_len used
  *   shards     : [batch][n_validators][shard_stride] bytes, shard_len used
  *   present    : [batch][n] bytes, 1 = shard present (indices >= n_validators
@@ -152,6 +153,119 @@ struct NPRSResult ECCR_AMD_reconstruct_batch_patterns(
     unsigned long shard_stride, const uint8_t *d_present, const uint16_t *d_err_log,
     const uint32_t *d_pattern, unsigned long batch, uint8_t *d_out, unsigned long out_stride,
     void *stream);
+
+/* ---- ragged batches: payloads of unequal length in one call -----------------
+ * The batch calls above take `batch` payloads of one length.  The ragged calls
+ * take a device-resident array of `batch` items, one per payload, each with
+ * its own length and its own place in the buffers, and run them in one launch
+ * whose work queue spans every item: a 15-byte item and a 10 MB item share the
+ * launch and finish together.  Results are bit-exact with the uniform calls
+ * (and ec-cpp) item by item.
+ *
+ * Contract, the same for every n_validators: payload_off, shard_off and
+ * shard_stride are multiples of 16, the buffers they refer to (d_payloads,
+ * d_shards, d_out; for the reconstruct also d_present and d_err_log) are 16-B
+ * aligned, d_items is 8-B aligned, and the items' regions do not overlap (not
+ * checked).  Lengths are stated per item; the call states their maximum.
+ *
+ * Validation.  What the host can see is checked on the host before anything is
+ * launched, with the usual tags and an ECCR_AMD_last_error text: n_validators;
+ * a NULL or misaligned buffer, batch == 0 or >= 2^31, a work-queue size
+ * batch x tiles(maximum) that reaches 2^32 (BAD_PAYLOAD; a tile is 64 shard
+ * columns of 2 bytes for n_validators 766 .. 1024); a maximum of 0 (BAD_PAYLOAD
+ * for the encode, NON_UNIFORM_CHUNKS for the reconstruct).  The items live on
+ * the device, so they are checked on the device: an item that breaks the
+ * contract -- length 0 or above the stated maximum, odd shard_len,
+ * shard_stride below the item's shard length, a field that is no multiple of
+ * 16 -- is skipped as a whole: nothing of it is read or written, the other
+ * items are unaffected.  d_status (device, uint32_t[2], nullable) receives
+ * {number of such items, lowest such index} on every call, {0, 0} when there
+ * are none.  ECCR_AMD_ragged_check runs the same test on a host copy.
+ *
+ * Workspace.  Unlike the uniform encode, a ragged call always needs device
+ * scratch (the plan of the call lives in it: 4 bytes per item, plus what the
+ * kernel needs).  The plain calls take it from the scratch private to
+ * (device, stream), as every plain call does; the _ws calls take the caller's:
+ * 256-B aligned, at least ECCR_AMD_*_ragged_workspace_bytes for the same
+ * n_validators, batch and maximum, else UNKNOWN_CODE_PARAM (encode) /
+ * UNKNOWN_RECONSTRUCTION with nothing launched.  Both forms are asynchronous
+ * on `stream`; the _ws forms allocate nothing and, after one warm call, can be
+ * captured into a hipGraph: every word of the plan is rebuilt by a kernel on
+ * each replay from the item array's contents at that time, so the items may
+ * change between replays (same batch and maxima).
+ *
+ * n_validators 766 .. 1024 run kernels of their own (the uniform calls' fast
+ * kernels on the ragged work queue); every other n_validators runs the
+ * generic kernels.  Work is handed out in tiles of 64 pieces / columns there,
+ * so a batch made of tiny payloads only is better served by the uniform
+ * calls, which pick packed kernels for it. */
+typedef struct ECCR_AMD_RaggedItem { /* 40 bytes */
+  uint64_t payload_off;  /* encode: offset of the payload in d_payloads;
+                            reconstruct: offset in d_out where shard_len * k
+                            bytes are written (zero-padded, as the reference) */
+  uint64_t payload_len;  /* encode: > 0, <= max_payload_len.  reconstruct: ignored */
+  uint64_t shard_off;    /* offset in d_shards of this item's
+                            [n_validators][shard_stride] rows */
+  uint64_t shard_len;    /* reconstruct: even, > 0, <= max_shard_len.  encode:
+                            ignored (ECCR_AMD_shard_len(n_validators, payload_len)) */
+  uint64_t shard_stride; /* >= the item's shard length */
+} ECCR_AMD_RaggedItem;
+
+/* payloads -> shard rows, item by item.  d_status nullable. */
+struct NPRSResult ECCR_AMD_encode_ragged(unsigned long n_validators, const uint8_t *d_payloads,
+                                         const ECCR_AMD_RaggedItem *d_items, unsigned long batch,
+                                         unsigned long max_payload_len, uint8_t *d_shards,
+                                         uint32_t *d_status, void *stream);
+struct NPRSResult ECCR_AMD_encode_ragged_ws(unsigned long n_validators, const uint8_t *d_payloads,
+                                            const ECCR_AMD_RaggedItem *d_items, unsigned long batch,
+                                            unsigned long max_payload_len, uint8_t *d_shards,
+                                            uint32_t *d_status, void *d_workspace,
+                                            unsigned long workspace_bytes, void *stream);
+
+/* shard rows -> shard_len * k output bytes, item by item.  d_present /
+ * d_err_log / d_pattern exactly as in ECCR_AMD_reconstruct_batch_ws: row b (or
+ * row d_pattern[b]) is item b's erasure pattern and locator, the locator
+ * calls above are used as they are.  As there, an item with fewer than k
+ * present shards yields unspecified bytes, and missing shards are never read. */
+struct NPRSResult ECCR_AMD_reconstruct_ragged(unsigned long n_validators, const uint8_t *d_shards,
+                                              const ECCR_AMD_RaggedItem *d_items,
+                                              const uint8_t *d_present, const uint16_t *d_err_log,
+                                              const uint32_t *d_pattern, unsigned long batch,
+                                              unsigned long max_shard_len, uint8_t *d_out,
+                                              uint32_t *d_status, void *stream);
+struct NPRSResult ECCR_AMD_reconstruct_ragged_ws(unsigned long n_validators, const uint8_t *d_shards,
+                                                 const ECCR_AMD_RaggedItem *d_items,
+                                                 const uint8_t *d_present, const uint16_t *d_err_log,
+                                                 const uint32_t *d_pattern, unsigned long batch,
+                                                 unsigned long max_shard_len, uint8_t *d_out,
+                                                 uint32_t *d_status, void *d_workspace,
+                                                 unsigned long workspace_bytes, void *stream);
+
+/* Workspace of a ragged call in bytes: never 0 for valid parameters, monotone
+ * in batch and in the maximum; 0 for invalid ones (n_validators, batch == 0
+ * or >= 2^31, a maximum of 0), which the calls themselves report. */
+unsigned long ECCR_AMD_encode_ragged_workspace_bytes(unsigned long n_validators, unsigned long batch,
+                                                     unsigned long max_payload_len);
+unsigned long ECCR_AMD_reconstruct_ragged_workspace_bytes(unsigned long n_validators,
+                                                          unsigned long batch,
+                                                          unsigned long max_shard_len);
+
+/* The device-side item validation on a host copy of the items (host-only, no
+ * device needed): status = {items that break the contract, lowest such index},
+ * {0, 0} when there are none.  max_len: max_payload_len (reconstruct == 0) or
+ * max_shard_len (reconstruct != 0).  Buffer alignment and overlaps are not its
+ * business.  BAD_PAYLOAD for a NULL argument or batch == 0 / >= 2^31. */
+struct NPRSResult ECCR_AMD_ragged_check(unsigned long n_validators, const ECCR_AMD_RaggedItem *h_items,
+                                        unsigned long batch, unsigned long max_len, int reconstruct,
+                                        uint32_t status[2]);
+
+/* The kernel a ragged call launches after its plan kernel (ragged_plan): it
+ * depends on n_validators only.  A static string, one of encode_k256w_ragged,
+ * encode_g_ragged, reconstruct_n1024x_ragged, reconstruct_g_ragged, or NULL for
+ * an invalid n_validators.  Host-only; as ECCR_AMD_encode_kernel below, for
+ * tests and triage, not a stable part of the interface. */
+const char *ECCR_AMD_encode_ragged_kernel(unsigned long n_validators);
+const char *ECCR_AMD_reconstruct_ragged_kernel(unsigned long n_validators);
 
 /* ---- diagnostics ---------------------------------------------------------
  * The name of the kernel ECCR_AMD_encode_batch / ECCR_AMD_reconstruct_batch

@@ -49,15 +49,20 @@ Build: scripts/build_var.sh diag_KIND "" enc_k256w.hip=OUT/enc_k256w.hip enc_w_c
 import os
 import sys
 
+sys.path.insert(0, __file__.rsplit("/", 1)[0])
+from flat import flat  # noqa: E402
+
 ROOT = __file__.rsplit("/scripts/", 1)[0]
 CS = f"{ROOT}/erasure-coding-crust_amd/csrc"
 kind, out = sys.argv[1], sys.argv[2]
 os.makedirs(out, exist_ok=True)
-enc = open(f"{CS}/enc_k256w.hip").read()
+# enc_k256w.hip and dec_n1024x.hip with their shared bodies (enc_k256w_tile.inc,
+# dec_n1024x_tile.inc and the headers beside them) in one source each: flat.py
+enc = flat("enc_k256w.hip")
 com = open(f"{CS}/enc_w_common.hpp").read()
 cim = open(f"{CS}/cimg.hpp").read()
 dec = open(f"{CS}/dec_n1024.hip").read()
-decx = open(f"{CS}/dec_n1024x.hip").read()
+decx = flat("dec_n1024x.hip")
 
 
 READER = '''
@@ -98,17 +103,17 @@ for k in kinds:
         enc = rep(enc, "const auto rsync = [&]() __attribute__((always_inline)) { lds_barrier(); };",
                   "const auto rsync = [&]() __attribute__((always_inline)) { asm volatile(\"\" ::: \"memory\"); };")
     elif k == "static":
-        enc = rep(enc, "  uint32_t cur = __builtin_amdgcn_readfirstlane(*slot);", "  uint32_t cur = blockIdx.x;")
-        enc = rep(enc, "      next = __builtin_amdgcn_readfirstlane(*slot);", "      next = cur + gridDim.x;")
+        enc = rep(enc, "  Tile cur = geo.read(slot).t;", "  Tile cur = blockIdx.x;")
+        enc = rep(enc, "      next = geo.read(slot).t;", "      next = cur + gridDim.x;")
     elif k == "wdyn":
-        take = ("[&]() { uint32_t v_ = 0; if ((tid0 & 63) == 0) v_ = atomicAdd(tick + 32 + 32 * (tid0 >> 6), 1u);"
+        take = ("[&]() { uint32_t v_ = 0; if ((tid0 & 63) == 0) v_ = atomicAdd(geo.tick + 32 + 32 * (tid0 >> 6), 1u);"
                 " return __builtin_amdgcn_readfirstlane(v_); }()")
-        enc = rep(enc, "  uint32_t cur = __builtin_amdgcn_readfirstlane(*slot);", f"  uint32_t cur = {take};")
+        enc = rep(enc, "  Tile cur = geo.read(slot).t;", f"  Tile cur = {take};")
         # the next tile's ticket taken at the tile start (lane 0 of each wave),
         # read at its end: the atomic's latency hidden as in the product
-        enc = rep(enc, "    if (tid0 == 0) taken = tick ? atomicAdd(tick, 1u) : cur + gridDim.x;",
-                  "    if ((tid0 & 63) == 0) taken = atomicAdd(tick + 32 + 32 * (tid0 >> 6), 1u);")
-        enc = rep(enc, "      next = __builtin_amdgcn_readfirstlane(*slot);", "      next = __builtin_amdgcn_readfirstlane(taken);")
+        enc = rep(enc, "    if (tid0 == 0) taken = geo.next_ticket(cur);",
+                  "    if ((tid0 & 63) == 0) taken = atomicAdd(geo.tick + 32 + 32 * (tid0 >> 6), 1u);")
+        enc = rep(enc, "      next = geo.read(slot).t;", "      next = __builtin_amdgcn_readfirstlane(taken);")
         # one counter per wave index, each on its own 128-B line (8 on one
         # line serialise in L2: ~6 ns per atomic); 1152 B of scratch, zeroed by
         # the shared launch tail: every kernel launched through it gets them
@@ -148,7 +153,7 @@ for k in kinds:
         enc = rep(enc, "  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];\n",
                   "  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];\n"
                   "  const uint64_t clk_t0 = __builtin_amdgcn_s_memtime(), clk_r0 = __builtin_amdgcn_s_memrealtime();\n")
-        enc = rep(enc, "  }\n}\n\nhipError_t launch_encode_k256w", "  }\n" + CLK_END + "}\n\nhipError_t launch_encode_k256w")
+        enc = rep(enc, "  }\n}\n}\n\nhipError_t launch_encode_k256w", "  }\n" + CLK_END + "}\n}\n\nhipError_t launch_encode_k256w")
         enc += READER
     elif k == "dnobar":
         dec = rep(dec, "    lds_barrier();  // previous tile's readers of the regions are done (LDS only)\n", "")
@@ -176,14 +181,14 @@ for k in kinds:
         extra["dec_n1024x.hip"] = decx
     elif k == "xwdyn":
         W = "(tid0 & 63) == 0"
-        decx = rep(decx, "  if (tid0 == 0) taken = gridDim.x + atomicAdd(tick, 1u);\n",
-                   f"  if ({W}) taken = gridDim.x + atomicAdd(tick + 32 + 32 * (tid0 >> 6), 1u);\n")
-        decx = rep(decx, "  if (tid0 == 0) *slot = taken;  // read after the first tile's region barrier\n", "")
-        decx = rep(decx, "      nxt = __builtin_amdgcn_readfirstlane(*slot);\n"
-                         "      if (tid0 == 0) taken = gridDim.x + atomicAdd(tick, 1u);  // the tile after nxt\n",
-                   "      nxt = __builtin_amdgcn_readfirstlane(taken);\n"
-                   f"      if ({W}) taken = gridDim.x + atomicAdd(tick + 32 + 32 * (tid0 >> 6), 1u);\n")
-        decx = rep(decx, "    if (tid0 == 0) *slot = taken;\n", "")
+        decx = rep(decx, "  if (tid0 == 0) taken = geo.first_ticket();\n",
+                   f"  if ({W}) taken = gridDim.x + atomicAdd(geo.tick + 32 + 32 * (tid0 >> 6), 1u);\n")
+        decx = rep(decx, "  if (geo.publishes(tid0)) geo.publish(slot, taken, tid0);  // read after the first tile's region barrier\n", "")
+        decx = rep(decx, "      nxt = geo.read(slot);\n"
+                         "      if (tid0 == 0) taken = geo.next_ticket();  // the tile after nxt\n",
+                   "      nxt = {uint32_t(__builtin_amdgcn_readfirstlane(taken))};\n"
+                   f"      if ({W}) taken = gridDim.x + atomicAdd(geo.tick + 32 + 32 * (tid0 >> 6), 1u);\n")
+        decx = rep(decx, "    if (geo.publishes(tid0)) geo.publish(slot, taken, tid0);\n", "")
         decx = rep(decx, "return n1024_tick_offset(p, batch) + 256; }", "return n1024_tick_offset(p, batch) + 2048; }")
         decx = rep(decx, "launch_zero_counters(tick, sizeof(uint32_t), s)", "launch_zero_counters(tick, 2048, s)")
         extra["dec_n1024x.hip"] = decx
@@ -193,7 +198,7 @@ for k in kinds:
         extra["dec_n1024x.hip"] = decx
     elif k.startswith("kclk:"):
         fname = k.split(":", 1)[1]
-        src = open(f"{CS}/{fname}").read()
+        src = flat(fname)
         src = rep(src, "namespace ecamd {\nnamespace {", "namespace ecamd {\n__device__ unsigned long long g_stamp[16];\nnamespace {")
         i = src.index("  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];\n")
         body = src.rindex("{\n", 0, i) + 2  # the kernel's opening brace

@@ -11,6 +11,9 @@ ECCR_DIAG_stamps(out, n, reset) (scripts/variants/stamp_run.py reads it).
 Build with scripts/build_var.sh NAME "" enc_k256.hip=OUT.hip (or dec_n1024.hip)."""
 import sys
 
+sys.path.insert(0, __file__.rsplit("/", 1)[0])
+from flat import flat  # noqa: E402
+
 ROOT = __file__.rsplit("/scripts/", 1)[0]
 kind, out = sys.argv[1], sys.argv[2]
 READER = '''
@@ -74,9 +77,9 @@ elif kind == "dec":
             "    __builtin_amdgcn_s_setprio(0);  // the next tile's gather: equal\n    STAMP(4);\n  }\n" + FLUSH)
     names = ["gather", "barriers", "ifft", "deriv+fft", "output"]
 elif kind == "encw":
-    s = open(f"{ROOT}/erasure-coding-crust_amd/csrc/enc_k256w.hip").read()
+    s = flat("enc_k256w.hip")  # the kernel with its shared body (enc_k256w_tile.inc) in one source
     s = rep(s, "namespace ecamd {\nnamespace {", "namespace ecamd {\n__device__ unsigned long long g_stamp[16];\nnamespace {")
-    s = rep(s, "  __syncthreads();\n\n  const uint64_t npieces", "  __syncthreads();\n" + STAMP + "\n  const uint64_t npieces")
+    s = rep(s, "  __syncthreads();\n\n  const auto pre = geo.prepare();", "  __syncthreads();\n" + STAMP + "\n  const auto pre = geo.prepare();")
     s = rep(s, "    const auto rsync = [&]() __attribute__((always_inline)) { lds_barrier(); };",
             "    const auto rsync = [&]() __attribute__((always_inline)) { STAMP(3); lds_barrier(); STAMP(1); };")
     # both store lambdas (store, store_last)
@@ -84,7 +87,7 @@ elif kind == "encw":
     s = rep(s, "      __builtin_amdgcn_s_setprio(0);\n    };", "      __builtin_amdgcn_s_setprio(0);\n      STAMP(2);\n    };", 3)
     s = rep(s, "    // ---- systematic shards 0..255 = the data symbols (poly_encoder.hpp:239)\n",
             "    STAMP(0);\n    // ---- systematic shards 0..255 = the data symbols (poly_encoder.hpp:239)\n")
-    s = rep(s, "  }\n}\n\nhipError_t launch_encode_k256w", "  }\n" + FLUSH + "}\n\nhipError_t launch_encode_k256w")
+    s = rep(s, "  }\n}\n}\n\nhipError_t launch_encode_k256w", "  }\n" + FLUSH + "}\n}\n\nhipError_t launch_encode_k256w")
     names = ["load", "barrier", "stores", "compute"]
 elif kind == "decw":
     # the two-workgroup reconstruct_n1024w: in dec_n1024.hip as of commit
