@@ -121,10 +121,10 @@ __global__ void __launch_bounds__(THREADS) reconstruct_n1024(
   const uint32_t tid0 = threadIdx.x, wave = tid0 >> 6;
   uint8_t *my = regions + wave * REG_BYTES;
 
-  // multiply tables for skew indices 0..1022: the prebuilt LDS image 0
-  // (DevTables::timg), one coalesced 80 KB copy instead of a 1023-entry gather
-  // through the skews (that gather was ~10 us of every launch; small calls pay it)
-  Tabs::copy_image<THREADS>(tabs, kF9 ? t.timg_f9 : t.timg_t, tid0);  // F9 kind 0
+  // multiply tables for skew indices 0..1022: the prebuilt tower image 0 in
+  // its F9 variant (DevTables::timg_f9), one coalesced 80 KB copy instead of a
+  // 1023-entry gather (that gather was ~10 us of every launch; small calls pay it)
+  Tabs::copy_image<THREADS>(tabs, t.timg_f9, tid0);  // F9 kind 0
   __syncthreads();
 
   const uint64_t ncols = slen / 2;

@@ -78,7 +78,6 @@ __device__ __forceinline__ void tab_at(const uint8_t *, uint32_t lin, SubTab &T)
 }
 constexpr int SUB = tower_sub_min(0);
 // IFFT stage 1 with F9 tables (F9 image kind 0)
-constexpr bool kF9 = true;
 __device__ __forceinline__ void tab_at(const uint8_t *, uint32_t lin, F9Tab &T) {
   lds_f9tab_abs<Tabs::kPlane>(lin, T);
 }
@@ -93,13 +92,13 @@ __device__ __forceinline__ void ib(S16 &s, int a, int b, const F9Tab &T) {
 // ahead of its use so a table load is always in flight behind the multiplies.
 template <int B0>
 __device__ __forceinline__ void ipass4(S16 &s, const uint8_t *tabs, uint32_t lb) {
-  Tab T[2];      // stages < SUB: general tables
-  F9Tab F[2];    // stage 1 (kF9): F9 tables
+  Tab T[2];      // stage 0: general tables
+  F9Tab F[2];    // stage 1: F9 tables
   SubTab U[2];   // stages >= SUB: subfield tables
   const auto fetch = [&](int t, int blk, int slot) __attribute__((always_inline)) {
     const uint32_t a = lb ^ tlin(skew_idx(uint32_t(blk) << B0, B0 + t));
     if (B0 + t >= SUB) tab_at(tabs, a, U[slot]);
-    else if (kF9 && B0 + t == 1) tab_at(tabs, a, F[slot]);
+    else if (B0 + t == 1) tab_at(tabs, a, F[slot]);
     else tab_at(tabs, a, T[slot]);
   };
   fetch(0, 0, 0);
@@ -114,7 +113,7 @@ __device__ __forceinline__ void ipass4(S16 &s, const uint8_t *tabs, uint32_t lb)
 #pragma unroll
       for (int i = 0; i < d; ++i) {
         if (B0 + t >= SUB) ib(s, blk + i, blk + i + d, U[k & 1]);
-        else if (kF9 && B0 + t == 1) ib(s, blk + i, blk + i + d, F[k & 1]);
+        else if (B0 + t == 1) ib(s, blk + i, blk + i + d, F[k & 1]);
         else ib(s, blk + i, blk + i + d, T[k & 1]);
       }
     }

@@ -88,7 +88,7 @@ Lin n4096_lin(int nq) {
   return lin;
 }
 
-// Per payload, the LDS image (LdsTabs<1024> layout, as DevTables::timg) of
+// Per payload, the LDS image (LdsTabs<1024> layout, as DevTables::timg_t) of
 // its output tables E[y], y < 1024 (decode_main:185-188): the k = 1024
 // reconstruct fills its output tables with one linear LDS-DMA per tile
 // instead of a per-tile gather of 1024 indexed 80-byte tables (two dependent

@@ -362,7 +362,7 @@ struct LdsTabs {
       T.t[4 * q + 3] = v.w;
     }
   }
-  // cooperative copy of a prebuilt image (DevTables::timg) of ENTRIES entries:
+  // cooperative copy of a prebuilt image (DevTables::timg_t, timg_f9) of ENTRIES entries:
   // every load issued before the first store
   template <int THREADS>
   __device__ static __forceinline__ void copy_image(uint8_t *base, const uint8_t *img,

@@ -68,9 +68,8 @@ constexpr uint32_t kEImg512Stage[3] = {0, 20480, 30720};
 constexpr uint32_t kEImg256Bytes = 10240, kEImg256Cosets = 4;
 
 struct DevTables {
-  const uint16_t *skews = nullptr;     // 65535
+  const uint16_t *skews = nullptr;     // 65535; no kernel reads it (they use mslot)
   const MulTab *mtab = nullptr;        // 65536
-  const uint8_t *timg = nullptr;       // kTabImages x kTabImageBytes
   const MulTab *mtab_tin = nullptr;    // 65536, symbols in, tower out
   const MulTab *mtab_tout = nullptr;   // 65536, tower in, symbols out
   const uint8_t *timg_t = nullptr;     // kTabImages x kTabImageBytes, tower images
@@ -198,10 +197,11 @@ hipError_t launch_systematic_tiny(const CodeParams &p, const uint8_t *h_shards, 
                                   uint8_t *out, hipStream_t s, HostSig *sig);
 hipError_t warm_encode_tiny(hipStream_t s);  // device set-up: the first launches of the tiny kernels
 
-// specialised kernels (enc_k256.hip)
+// k = 256, n = 1024 / 2048 (enc_k256.hip, enc_k256w.hip, enc_kw.hip)
 bool k256_applicable(const CodeParams &p);
-// tile sizes the choosers test (static_asserts beside the kernels): pieces per
-// tile of the unpacked k = 256 encodes' dispatch, columns per tile of
+// tile sizes the choosers test (static_asserts beside the kernels): the
+// fewest pieces per payload from which k = 256 runs unpacked (encode_k256w /
+// encode_kw<8>), which is also the packed kernel's tile; columns per tile of
 // reconstruct_n1024<false>, the fewest columns reconstruct_n1024x takes, and
 // the fewest from which it runs its 16-wave form (n1024x_waves: measured; at
 // 96 and 144 columns, two and three whole 12-wave tiles, the 12-wave form is
@@ -214,10 +214,11 @@ constexpr size_t kK256Tile = 128, kN1024Cols = 32, kN1024xMinCols = 48, kN1024x1
 hipError_t launch_encode_k256(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,
                               size_t plen, size_t pstride, size_t batch, uint8_t *d_shards,
                               size_t sstride, hipStream_t s);
-size_t k256_scratch_bytes(const CodeParams &p);
 // encode_k256w (n = 1024, unpacked): two 8-wave workgroups per
 // CU on the compact image, tiles scheduled dynamically from a counter in
-// `scratch` (enc_k256w.hip)
+// `scratch` (enc_k256w.hip); k256_scratch_bytes: that counter, and the one of
+// encode_kw<8> at n = 2048 (nullable: static tile schedule)
+size_t k256_scratch_bytes(const CodeParams &p);
 hipError_t launch_encode_k256w(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,
                                size_t plen, size_t pstride, size_t batch, uint8_t *d_shards,
                                size_t sstride, void *scratch, hipStream_t s);

@@ -18,7 +18,6 @@ struct DeviceState {
   int id = -1;
   uint16_t *skews = nullptr;
   MulTab *mtab = nullptr;
-  uint8_t *timg = nullptr;
   MulTab *mtab_t = nullptr;  // mtab_tin, then mtab_tout
   uint8_t *timg_t = nullptr;
   uint8_t *timg_f9 = nullptr;
@@ -101,16 +100,14 @@ DeviceState *device_state() {
                         hipMemcpyHostToDevice),
               "upload mtab"))
     return nullptr;
-  // LDS table images (ec_kernels.hpp kTabImages): LdsTabs<1024>::addr layout;
-  // img_t: the tower images (subfield tables at stages >= tower_sub_min(q))
-  std::vector<uint8_t> img(kTabImages * kTabImageBytes, 0), img_t(kTabImages * kTabImageBytes, 0);
+  // LDS table images (ec_kernels.hpp kTabImages), LdsTabs<1024>::addr layout:
+  // the tower images (subfield tables at stages >= tower_sub_min(q))
+  std::vector<uint8_t> img_t(kTabImages * kTabImageBytes, 0);
   for (int q = 0; q < kTabImages; ++q)
     for (uint32_t i = 0; i < 1023; ++i) {
       const uint32_t c = f.skews[1024 * q + i];
-      const uint8_t *src = reinterpret_cast<const uint8_t *>(&f.mtab[c]);
       const uint32_t sw = (i ^ (i >> 4) ^ (i >> 8)) & 15;
       const size_t slot = size_t(q) * kTabImageBytes + ((i >> 4) << 8) + (sw << 4);
-      for (uint32_t plane = 0; plane < 5; ++plane) std::memcpy(&img[slot + plane * 16384], src + 16 * plane, 16);
       if (__builtin_ctz(1024 * q + i + 1) >= tower_sub_min(q)) {
         const MulTabSub u = f.sub_tab(c);
         std::memcpy(&img_t[slot], &u.w[0], 16);
@@ -188,10 +185,7 @@ DeviceState *device_state() {
       !hip_ok(hipMemcpy(st->timg_f9, img_f9.data(), img_f9.size(), hipMemcpyHostToDevice),
               "upload F9 images"))
     return nullptr;
-  if (!hip_ok(hipMalloc(&st->timg, img.size()), "hipMalloc(table images)") ||
-      !hip_ok(hipMemcpy(st->timg, img.data(), img.size(), hipMemcpyHostToDevice),
-              "upload table images") ||
-      !hip_ok(hipMalloc(&st->timg_t, img_t.size()), "hipMalloc(tower images)") ||
+  if (!hip_ok(hipMalloc(&st->timg_t, img_t.size()), "hipMalloc(tower images)") ||
       !hip_ok(hipMemcpy(st->timg_t, img_t.data(), img_t.size(), hipMemcpyHostToDevice),
               "upload tower images"))
     return nullptr;
@@ -228,7 +222,6 @@ DevTables device_tables(DeviceState *d) {
   DevTables t;
   t.skews = d->skews;
   t.mtab = d->mtab;
-  t.timg = d->timg;
   t.mtab_tin = d->mtab_t;
   t.mtab_tout = d->mtab_t + kFieldSize;
   t.timg_t = d->timg_t;

@@ -1,20 +1,19 @@
-// enc_k256.hip — encode kernel specialised for k = 256, n = 1024
-// (n_validators 766..1024, the BASELINE headline configuration).
+// enc_k256.hip — the packed k = 256 encode: small payloads,
+// and payload or shard pitches the 16-B paths of encode_k256w (n = 1024) and
+// encode_kw<8> (n = 2048) cannot take.  Loads and stores take any payload
+// address and any even shard address.
 //
-// Work decomposition:
-//  * persistent: one 1024-thread workgroup (16 waves, 4 per SIMD) per CU,
-//    looping over tiles of 128 consecutive pieces (piece = 512 payload bytes
-//    = 256 GF(2^16) symbols);
-//  * wave w owns pieces [8w, 8w+8) of the tile: 2 "instances" (lanes 0-31 /
-//    32-63) x 1 byte-planar group (registers) x 4 pieces;
-//  * within an instance, lane q holds 8 of the 256 positions in registers:
-//    every radix-8 pass runs 3 butterfly stages in registers, then the wave
+//  * one 1024-thread workgroup (16 waves, 4 per SIMD) per CU on the 80 KB
+//    skew-slot F9 image (kind 1), resident in LDS; at n = 2048
+//    tower image 1 replaces it by LDS-DMA for the cosets at 1024 and above;
+//  * a wave transforms 8 pieces (piece = 512 payload bytes = 256 GF(2^16)
+//    symbols): 2 "instances" (lanes 0-31 / 32-63) x 4 byte-planar pieces;
+//    lane q of an instance holds 8 of the 256 positions in registers, every
+//    radix-8 pass runs 3 butterfly stages in registers, then the wave
 //    re-distributes positions through its private LDS region;
-//  * multiplies: v_perm tables (ec_device.hpp) for every skew the k=256 /
-//    n=1024 code uses (1023 x 80 B) are resident in LDS for the whole kernel;
-//  * shard stores: each wave stages its 8 pieces x 256 rows in its own LDS
-//    region; all waves then write 256-byte contiguous row segments
-//    (global_store_dwordx4, 16 B per lane).
+//  * a wave stages its 8 pieces x 256 rows in that region for the row stores.
+// PK = 2 (n = 1024) runs the waves independently, PK = 1 (n = 2048) in
+// 128-piece tiles: see the comment above the kernel.
 // Butterflies, skew indices and the encodeLow structure follow
 // include/ec-cpp/additive_fft.hpp:99-141 and poly_encoder.hpp:217-240.
 #include <hip/hip_runtime.h>
@@ -29,17 +28,16 @@ namespace ecamd {
 namespace {
 
 constexpr int K = 256;
-// one byte-planar group per lane (GP = 1) and 16 waves: 4 waves/SIMD (<= 128
-// VGPRs) for latency hiding; the tile is 128 pieces
-constexpr int WAVES = 16 / GP;
+// 16 waves: 4 waves/SIMD (<= 128 VGPRs) for latency hiding
+constexpr int WAVES = 16;
 constexpr int THREADS = 64 * WAVES;
-constexpr int TILE = 8 * GP * WAVES;  // pieces per tile
+constexpr int TILE = 128;  // pieces per tile (PK = 1): 8 per wave
 using Tabs = LdsTabs<1024>;
 constexpr int TAB_REGION = Tabs::kBytes;  // skew idx 0..1022
-constexpr int XCH_BYTES = 256 * 16 * GP;   // per-wave exchange region
+constexpr int XCH_BYTES = 4096;           // per-wave exchange region
 constexpr int LDS_BYTES = TAB_REGION + WAVES * XCH_BYTES;
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
-static_assert(TILE == 128 && 256 * 256 <= WAVES * XCH_BYTES, "staging fits the exchange regions");
+static_assert(TILE == 8 * WAVES && 256 * 256 <= WAVES * XCH_BYTES, "staging fits the exchange regions");
 
 // GF(2)-linear part of the swizzled table address (LdsTabs::addr without the
 // plane term): tlin(a | b) = tlin(a) ^ tlin(b) for disjoint a, b.  A table index
@@ -80,10 +78,9 @@ struct TabSel<true> {
 };
 template <int M, int SM>
 using TabAt = typename TabSel<(M >= SM)>::type;
-// F9 tables (F9 image kind 1) where F is set
+// F9 tables (F9 image kind 1) where F is set: per coset
 template <int M, int SM, bool F>
 using TabAtF = std::conditional_t<F, F9Tab, TabAt<M, SM>>;
-constexpr bool kF9 = true;
 
 __device__ __forceinline__ void lds_tab_at(const uint8_t *lds, uint32_t lin, F9Tab &T) {
 #pragma unroll
@@ -238,7 +235,7 @@ __device__ __forceinline__ void stage_own(const State &s, uint8_t *xch, uint32_t
 #pragma unroll
   for (int r = 0; r < 8; ++r)
     *reinterpret_cast<uint2 *>(xch + soff(posA(q, r), wave) + 8 * inst) =
-        to_be(s.l[0][r], s.h[0][r]);
+        to_be(s.l[r], s.h[r]);
 }
 
 // one 16-B chunk (8 pieces) of a shard row at any even address: the widest
@@ -270,27 +267,19 @@ __device__ __forceinline__ void store_chunk_any(uint8_t *dst, const uint4 val, u
     if (uint64_t(e) < nvalid) *reinterpret_cast<uint16_t *>(dst + 2 * e) = uint16_t(w[e >> 1] >> (16 * (e & 1)));
 }
 
-// all waves: rows [s0, s0 + 256) from the 16 regions -> shards; lane =
-// (row-in-4, source wave c = 16-B chunk of pieces [8c, 8c + 8)): pieces
-// piece0 + 8c of the tile's payload (SH), or, packed, pieces [pc, pc + 8) of
-// the payload bc that owns flattened slot tile * TILE + 8c (computed here, not
-// kept live across the FFTs)
-// (The unpacked form, PACKED = false, is not instantiated any more: its shapes
-// run encode_k256w and encode_kw<8>.)
-template <bool PACKED>
+// packed tiles (PK = 1), all waves: rows [s0, s0 + 256) from the 16 regions ->
+// shards; lane = (row-in-4, source wave c = 16-B chunk of 8 pieces): pieces
+// [p, p + 8) of the payload bc that owns flattened slot tile * TILE + 8c
+// (computed here, not kept live across the FFTs)
 __device__ __forceinline__ void store_own(const uint8_t *xbase, uint8_t *SH, uint64_t sstride,
-                                          uint32_t s0, int nv, uint64_t piece0, uint64_t npieces,
-                                          uint32_t wave, uint32_t lane, uint64_t tile, uint32_t npp8,
+                                          uint32_t s0, int nv, uint64_t npieces, uint32_t wave,
+                                          uint32_t lane, uint64_t tile, uint32_t npp8,
                                           uint32_t batch) {
   asm volatile("" : "+v"(lane));  // recomputed here, not kept live across the FFTs
   const uint32_t c = lane & 15;
-  uint64_t p = piece0 + 8 * c;
-  if constexpr (PACKED) {
-    const uint32_t gc = uint32_t(tile) * TILE + 8 * c, bc = gc / npp8;
-    p = bc < batch ? gc % npp8 : npieces;  // past the batch: nothing to store
-    SH += uint64_t(bc < batch ? bc : 0) * uint64_t(nv) * sstride;
-  }
-  const bool wide = ((sstride | reinterpret_cast<uintptr_t>(SH)) & 15) == 0;  // 16-B aligned rows
+  const uint32_t gc = uint32_t(tile) * TILE + 8 * c, bc = gc / npp8;
+  const uint64_t p = bc < batch ? gc % npp8 : npieces;  // past the batch: nothing to store
+  SH += uint64_t(bc < batch ? bc : 0) * uint64_t(nv) * sstride;
   const uint8_t *src = xbase + c * XCH_BYTES;
 #pragma unroll
   for (int it = 0; it < 256 / (4 * WAVES); ++it) {
@@ -299,20 +288,7 @@ __device__ __forceinline__ void store_own(const uint8_t *xbase, uint8_t *SH, uin
     const uint32_t shard = s0 + v;
     if (int(shard) >= nv) continue;
     uint8_t *dst = SH + uint64_t(shard) * sstride + 2 * p;
-    if constexpr (PACKED) {
-      if (p < npieces) store_chunk_any(dst, val, npieces - p);
-    } else if (p + 8 <= npieces) {
-      if (wide) {
-        *reinterpret_cast<uint4 *>(dst) = val;
-      } else {
-        reinterpret_cast<uint2 *>(dst)[0] = make_uint2(val.x, val.y);
-        reinterpret_cast<uint2 *>(dst)[1] = make_uint2(val.z, val.w);
-      }
-    } else if (p < npieces) {
-      const uint32_t w[4] = {val.x, val.y, val.z, val.w};
-      for (uint64_t e = 0; e < npieces - p; ++e)
-        *reinterpret_cast<uint16_t *>(dst + 2 * e) = uint16_t(w[e >> 1] >> (16 * (e & 1)));
-    }
+    if (p < npieces) store_chunk_any(dst, val, npieces - p);
   }
 }
 
@@ -339,37 +315,34 @@ __device__ __forceinline__ void store_wave(const uint8_t *xch, uint8_t *shards, 
 }  // namespace
 
 // N = n: 1024 (n_validators 766..1024) or 2048 (1025..1533); the cosets at
-// 1024 and above use LDS table image 1 (skews 1024 .. 2046, DevTables::timg)
-// at offset sh - 1024, reloaded by LDS-DMA between the two coset loops
-// PK = 1, packed tiles (n = 2048 with small payloads, or payload / shard
-// pitches the 16-B path cannot take): tiles run over the flattened piece space
-// of the batch, payload b owning slots [b * npp8, b * npp8 + npieces) with
-// npp8 = pieces rounded up to 8, so a wave's 8 pieces (and each 16-B chunk of
-// a staged row) belong to one payload; loads and stores take any alignment.
-// PK = 2, packed waves (n = 1024, same cases): the waves run independently
-// over tasks of 8 consecutive pieces of the exactly flattened piece space
-// (payload b owns pieces [b * npp, (b + 1) * npp)), each staging and storing
-// its own rows (2-B stores, any payload per piece), no workgroup barrier in the
-// loop: 4096 one-piece payloads are 512 wave tasks (about 2 per CU) instead of
-// 4096 tiles (or 256 tiles of 8x-rounded slots).
+// 1024 and above use tower image 1 (skews 1024 .. 2046, DevTables::timg_t) at
+// offset sh - 1024, reloaded by LDS-DMA between the two coset loops.
+// PK = 1, packed tiles (n = 2048): tiles of 128 slots run over the flattened
+// piece space of the batch, payload b owning slots [b * npp8, b * npp8 +
+// npieces) with npp8 = pieces rounded up to 8, so a wave's 8 pieces (and each
+// 16-B chunk of a staged row) belong to one payload; all waves store the
+// tile's rows out of the 16 regions, between workgroup barriers.
+// PK = 2, packed waves (n = 1024): the waves run independently over tasks of 8
+// consecutive pieces of the exactly flattened piece space (payload b owns
+// pieces [b * npp, (b + 1) * npp)), each staging and storing its own rows
+// (2-B stores, any payload per piece), no workgroup barrier in the loop: 4096
+// one-piece payloads are 512 wave tasks (about 2 per CU) instead of 4096 tiles
+// (or 256 tiles of 8x-rounded slots).
 template <int N, int PK>
 __global__ void __launch_bounds__(THREADS) encode_k256(const uint8_t *__restrict__ payloads,
                                                        uint64_t plen, uint64_t pstride,
                                                        uint8_t *__restrict__ shards, uint64_t slen,
                                                        uint64_t sstride, int nv, uint32_t batch,
                                                        uint32_t npp8, DevTables t) {
+  static_assert(PK == 1 || PK == 2, "packed tiles or packed waves (the unpacked shapes run encode_k256w / encode_kw<8>)");
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   uint8_t *tabs = lds;
   const uint32_t tid0 = threadIdx.x;
   uint8_t *stg = lds + TAB_REGION;
 
-  // resident multiply tables for skew indices 0..1022 (all FFTs of k=256, n=1024)
-  // multiply tables for skew indices 0..1022: the prebuilt LDS image 0
-  // (DevTables::timg), one coalesced 80 KB copy instead of a 1023-entry gather
-  // through the skews (that gather was ~10 us of every launch; small calls pay it)
-  // the tower images: the transforms run in tower coordinates
-  // (image 0 as its F9 variant kind 1: DESIGN.md §2.8)
-  const uint8_t *const img0 = kF9 ? t.timg_f9 + kTabImageBytes : t.timg_t;
+  // multiply tables for skew indices 0..1022 in tower coordinates (DESIGN.md
+  // §2.7), F9 kind 1 (§2.8): one coalesced 80 KB copy of the prebuilt image
+  const uint8_t *const img0 = t.timg_f9 + kTabImageBytes;  // F9 kind 1
   Tabs::copy_image<THREADS>(tabs, img0, tid0);
   __syncthreads();
   [[maybe_unused]] int img = 0;
@@ -380,12 +353,8 @@ __global__ void __launch_bounds__(THREADS) encode_k256(const uint8_t *__restrict
     lds_barrier();
   };
 
-  constexpr bool PACKED = PK == 1;
   const uint64_t npieces = slen / 2;
-  const uint32_t tiles_pp = uint32_t((npieces + TILE - 1) / TILE);
-  const uint64_t total = PK == 2   ? (npieces * batch + 7) / 8
-                         : PACKED ? (uint64_t(npp8) * batch + TILE - 1) / TILE
-                                  : uint64_t(tiles_pp) * batch;
+  const uint64_t total = PK == 2 ? (npieces * batch + 7) / 8 : (uint64_t(npp8) * batch + TILE - 1) / TILE;
   // PK = 2: "tile" = this wave's task (a wave-uniform, scalar index)
   const uint32_t wave_s = __builtin_amdgcn_readfirstlane(tid0 >> 6);
   // (task t on workgroup t % grid, wave t / grid: a small batch spreads over
@@ -403,8 +372,7 @@ __global__ void __launch_bounds__(THREADS) encode_k256(const uint8_t *__restrict
       lds_barrier();
     }
   };
-  TileWalk walk(first, step, tiles_pp);  // PK = 0: payload and tile of `tile`
-  for (uint64_t tile = first; tile < total; tile += step, walk.advance()) {
+  for (uint64_t tile = first; tile < total; tile += step) {
     // lane ids made opaque per tile: per-lane LDS addresses are recomputed in the
     // loop instead of being hoisted out of it and spilled
     uint32_t tid = tid0;
@@ -416,101 +384,49 @@ __global__ void __launch_bounds__(THREADS) encode_k256(const uint8_t *__restrict
     xb.a = mswz(ulaneA(q, inst));
     xb.b = mswz(ulaneB(q, inst));
     xb.c = mswz(ulaneC(q, inst));
-    // unpacked: the tile is pieces [piece0, piece0 + 128) of payload b;
-    // packed: wave w's 8 pieces are pieces [pw, pw + 8) of payload bw (uniform),
-    // and the chunk a lane stores (source wave c) is pieces [pc, pc + 8) of bc
-    uint64_t b, piece0, bw = 0, pw = 0;
-    if constexpr (PACKED) {
+    // PK = 1: wave w's 8 pieces are pieces [pw, pw + 8) of payload bw (uniform);
+    // the chunk a lane stores belongs to its source wave's payload (store_own)
+    [[maybe_unused]] uint64_t bw = 0, pw = 0;
+    if constexpr (PK == 1) {
       const uint32_t gw = uint32_t(tile) * TILE + 8 * wave;  // < 2^32 (launch check)
       bw = gw / npp8;
       pw = gw % npp8;
-      b = bw;
-      piece0 = pw;
-    } else {
-      b = walk.b;
-      piece0 = walk.i * TILE;
     }
-    const uint8_t *P = payloads + b * pstride;
-    uint8_t *SH = PACKED ? shards : shards + b * uint64_t(nv) * sstride;  // packed: per chunk
+    [[maybe_unused]] const uint8_t *P = payloads + bw * pstride;
 
     const auto store = [&](uint32_t s0) __attribute__((always_inline)) {
       // the row stores (LDS reads + global stores) at raised issue priority:
       // a wave's stores leave before the other waves' next transform
-      // (B = 4096 encode 7.58 -> 7.39 ms; priority 3 the same)
       __builtin_amdgcn_s_setprio(1);
       if constexpr (PK == 2)
         store_wave(xch, shards, sstride, s0, nv, uint32_t(tile), uint32_t(npieces), batch, wave, lane);
       else
-        store_own<PACKED>(stg, SH, sstride, s0, nv, piece0, npieces, wave, lane, tile, npp8, batch);
+        store_own(stg, shards, sstride, s0, nv, npieces, wave, lane, tile, npp8, batch);
       __builtin_amdgcn_s_setprio(0);
     };
 
-    // A wave none of whose 8 pieces exist (the last, partial tile of a payload:
-    // 1 MB is 1954 pieces, its 16th tile has 34) skips the transforms and only
-    // takes part in the barriers, the image loads and the row stores of the
-    // others, in the same order as below (wave-uniform branch)
-    if constexpr (PK == 0) {
-      if (piece0 + 8 * wave_s >= npieces) {
-        rsync();  // tile start
-        rsync();  // systematic rows staged
-        store(0);
-        if constexpr (N > 1024) {
-          if (img != 0) {
-            load_image(0);
-            img = 0;
-          }
-        }
-        rsync();  // after IFFT pass A
-        const auto coset_idle = [&](uint32_t sh) __attribute__((always_inline)) {
-          rsync();  // after pass C
-          rsync();  // rows staged
-          store(sh);
-          __builtin_amdgcn_sched_barrier(0);
-        };
-        coset_idle(K);
-        for (uint32_t sh = 2 * K; sh < 1024u && int(sh) < nv; sh += K) coset_idle(sh);
-        if constexpr (N > 1024) {
-          for (uint32_t sh = 1024u; sh < uint32_t(N) && int(sh) < nv; sh += K) {
-            if (sh == 1024u) {
-              load_image(1);
-              img = 1;
-            }
-            coset_idle(sh);
-          }
-        }
-        continue;
-      }
-    }
-
-    // ---- load 8 pieces x 16 bytes (positions 8q..8q+7), zero past plen
+    // ---- load 4 pieces x 16 bytes (positions 8q..8q+7), zero past plen
     State s;
+    // A one-trip loop and its own copy of enc_w_common.hpp's to_state: the
+    // compiler unrolls the two loops inside it before it simplifies them, and
+    // every other spelling tried (no loop, to_state, a lambda) changes the
+    // instruction schedule of encode_k256<2048, 1>.
 #pragma unroll
-    for (int g = 0; g < GP; ++g) {
+    for (int once = 0; once < 1; ++once) {
       uint4 d[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         if constexpr (PK == 2) {
-          const uint32_t gp = uint32_t(tile) * 8 + inst * 4 * GP + g * 4 + u;  // < 2^32 (launch check)
+          const uint32_t gp = uint32_t(tile) * 8 + inst * 4 + u;  // < 2^32 (launch check)
           const uint32_t pb = gp / uint32_t(npieces), piece = gp % uint32_t(npieces);
           const uint64_t off = uint64_t(piece) * 2 * K + 16 * q;
           const bool ok = pb < batch && off < plen;
           d[u] = load16_any(payloads + uint64_t(ok ? pb : 0) * pstride + (ok ? off : 0), ok ? plen - off : 0);
-        } else if constexpr (PACKED) {
-          const uint64_t piece = pw + inst * 4 * GP + g * 4 + u;
+        } else {
+          const uint64_t piece = pw + inst * 4 + u;
           const uint64_t off = piece * 2 * K + 16 * q;
           const bool ok = bw < batch && piece < npieces && off < plen;
           d[u] = load16_any(P + (ok ? off : 0), ok ? plen - off : 0);
-        } else {
-          const uint64_t piece = piece0 + wave * 8 * GP + inst * 4 * GP + g * 4 + u;
-          const uint64_t off = piece * 2 * K + 16 * q;
-          if (off + 16 <= plen) {
-            d[u] = *reinterpret_cast<const uint4 *>(P + off);
-          } else {
-            uint32_t w[4] = {0, 0, 0, 0};
-            for (uint64_t e = off; e < plen && e < off + 16; ++e)
-              w[(e - off) >> 2] |= uint32_t(P[e]) << (8 * ((e - off) & 3));
-            d[u] = make_uint4(w[0], w[1], w[2], w[3]);
-          }
         }
       }
       // 4x4 byte transposes: dword j of each piece = (hi_{2j}, lo_{2j}, hi_{2j+1}, lo_{2j+1})
@@ -519,10 +435,10 @@ __global__ void __launch_bounds__(THREADS) encode_k256(const uint8_t *__restrict
         const uint32_t D0 = (&d[0].x)[j], D1 = (&d[1].x)[j], D2 = (&d[2].x)[j], D3 = (&d[3].x)[j];
         const uint32_t t0 = vperm(D1, D0, 0x05010400u), t1 = vperm(D1, D0, 0x07030602u);
         const uint32_t u0 = vperm(D3, D2, 0x05010400u), u1 = vperm(D3, D2, 0x07030602u);
-        s.h[g][2 * j] = vperm(u0, t0, 0x05040100u);
-        s.l[g][2 * j] = vperm(u0, t0, 0x07060302u);
-        s.h[g][2 * j + 1] = vperm(u1, t1, 0x05040100u);
-        s.l[g][2 * j + 1] = vperm(u1, t1, 0x07060302u);
+        s.h[2 * j] = vperm(u0, t0, 0x05040100u);
+        s.l[2 * j] = vperm(u0, t0, 0x07060302u);
+        s.h[2 * j + 1] = vperm(u1, t1, 0x05040100u);
+        s.l[2 * j + 1] = vperm(u1, t1, 0x07060302u);
       }
     }
 
@@ -535,7 +451,7 @@ __global__ void __launch_bounds__(THREADS) encode_k256(const uint8_t *__restrict
     {  // into tower coordinates
       const TowerK tk = tower_k();
 #pragma unroll
-      for (int r = 0; r < 8; ++r) s.l[0][r] = tower_lo(s.l[0][r], s.h[0][r], tk);
+      for (int r = 0; r < 8; ++r) s.l[r] = tower_lo(s.l[r], s.h[r], tk);
     }
 
     // ---- IFFT_256 (index 0): passes A (bits 0-2), B (3-5), C (6-7)
@@ -566,7 +482,7 @@ __global__ void __launch_bounds__(THREADS) encode_k256(const uint8_t *__restrict
       // the first stage's selector masks out of the coset loop (that costs ~50
       // VGPRs and forces spills); pass C's stage 7 reads it and writes s
 #pragma unroll
-      for (int r = 0; r < 8; ++r) asm volatile("" : "+v"(coef.l[0][r]), "+v"(coef.h[0][r]));
+      for (int r = 0; r < 8; ++r) asm volatile("" : "+v"(coef.l[r]), "+v"(coef.h[r]));
       fpassC(s, coef, tabs, off);
       rsync();  // previous coset's rows read out
       exchange<LC, LB>(s, xch, xb);
@@ -576,7 +492,7 @@ __global__ void __launch_bounds__(THREADS) encode_k256(const uint8_t *__restrict
       {  // back to symbol coordinates
         const TowerK tk = tower_k();
 #pragma unroll
-        for (int r = 0; r < 8; ++r) s.l[0][r] = tower_lo(s.l[0][r], s.h[0][r], tk);
+        for (int r = 0; r < 8; ++r) s.l[r] = tower_lo(s.l[r], s.h[r], tk);
       }
       stage_own(s, xch, q, inst, wave);
       rsync();
@@ -585,20 +501,20 @@ __global__ void __launch_bounds__(THREADS) encode_k256(const uint8_t *__restrict
     };
     using Sub0 = std::integral_constant<int, tower_sub_min(0)>;
     using Sub1 = std::integral_constant<int, tower_sub_min(1)>;
-    using F9on = std::integral_constant<bool, kF9>;
-    using F9off = std::integral_constant<bool, false>;
+    using F9 = std::true_type;
+    using NoF9 = std::false_type;
     // coset 1 (index 256): stage 1 skews are 128 + 2 (pos >> 2), subfield;
     // stage 0's elements 256..510 take F9 tables
-    coset(Sub0(), std::integral_constant<int, 1>(), F9on(), F9off(), K, K);  // (nv > 256 for k = 256)
+    coset(Sub0(), std::integral_constant<int, 1>(), F9(), NoF9(), K, K);  // (nv > 256 for k = 256)
     // cosets 2, 3: stage 1's elements 256..510 take F9 tables
-    for (uint32_t sh = 2 * K; sh < 1024u && int(sh) < nv; sh += K) coset(Sub0(), Sub0(), F9off(), F9on(), sh, sh);
+    for (uint32_t sh = 2 * K; sh < 1024u && int(sh) < nv; sh += K) coset(Sub0(), Sub0(), NoF9(), F9(), sh, sh);
     if constexpr (N > 1024) {
       for (uint32_t sh = 1024u; sh < uint32_t(N) && int(sh) < nv; sh += K) {
         if (sh == 1024u) {
           load_image(1);
           img = 1;
         }
-        coset(Sub1(), Sub1(), F9off(), F9off(), sh, sh & 1023u);
+        coset(Sub1(), Sub1(), NoF9(), NoF9(), sh, sh & 1023u);
       }
     }
   }
@@ -608,10 +524,7 @@ bool k256_applicable(const CodeParams &p) { return p.k == 256 && (p.n == 1024 ||
 
 static_assert(size_t(TILE) == kK256Tile, "choose_encode tests this tile");
 
-size_t k256_scratch_bytes(const CodeParams &) { return 256; }  // the unpacked kernels' tile counter
-
-// the packed kernel, PK = 2 at n = 1024 and PK = 1 at n = 2048 (the unpacked
-// shapes run encode_k256w and encode_kw<8>); choose_encode has checked the
+// PK = 2 at n = 1024 and PK = 1 at n = 2048; choose_encode has checked the
 // even shard base and pitch and the 2^32 bound of the flattened piece space
 hipError_t launch_encode_k256(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,
                               size_t plen, size_t pstride, size_t batch, uint8_t *d_shards,

@@ -1,5 +1,5 @@
 // enc_k256_common.hpp — pieces shared by the k = 256 encode kernels
-// (enc_k256.hip: the n = 1024 packed and n = 2048 forms) and, through
+// (enc_k256.hip: the packed kernel, n = 1024 and n = 2048) and, through
 // enc_w_common.hpp, by the two-workgroups-per-CU kernels, whose layouts are
 // the k = 256 ones (enc_k256w.hip, enc_kw.hip, enc_k512w.hip).  One
 // byte-planar group of 4 pieces per instance (lanes 0-31 / 32-63), 8 positions
@@ -14,10 +14,8 @@
 namespace ecamd {
 namespace {
 
-constexpr int GP = 1;  // byte-planar groups per lane
-
 struct State {
-  uint32_t l[GP][8], h[GP][8];  // [group][register]: low / high byte planes
+  uint32_t l[8], h[8];  // [register]: low / high byte planes
 };
 
 __device__ __forceinline__ void mul_any(uint32_t xl, uint32_t xh, const Tab &T, uint32_t &yl, uint32_t &yh) {
@@ -34,41 +32,32 @@ __device__ __forceinline__ void mul_any(uint32_t xl, uint32_t xh, const F9Tab &T
 
 template <typename T>
 __device__ __forceinline__ void ibfly(State &s, int ra, int rb, const T &Tb) {
-#pragma unroll
-  for (int g = 0; g < GP; ++g) {
-    s.l[g][rb] ^= s.l[g][ra];
-    s.h[g][rb] ^= s.h[g][ra];
-    mul_any(s.l[g][rb], s.h[g][rb], Tb, s.l[g][ra], s.h[g][ra]);
-  }
+  s.l[rb] ^= s.l[ra];
+  s.h[rb] ^= s.h[ra];
+  mul_any(s.l[rb], s.h[rb], Tb, s.l[ra], s.h[ra]);
 }
 
 template <typename T>
 __device__ __forceinline__ void fbfly(State &s, int ra, int rb, const T &Tb) {
-#pragma unroll
-  for (int g = 0; g < GP; ++g) {
-    mul_any(s.l[g][rb], s.h[g][rb], Tb, s.l[g][ra], s.h[g][ra]);
-    s.l[g][rb] ^= s.l[g][ra];
-    s.h[g][rb] ^= s.h[g][ra];
-  }
+  mul_any(s.l[rb], s.h[rb], Tb, s.l[ra], s.h[ra]);
+  s.l[rb] ^= s.l[ra];
+  s.h[rb] ^= s.h[ra];
 }
 
 __device__ __forceinline__ void bxor(State &s, int ra, int rb) {  // b ^= a (no multiply)
-#pragma unroll
-  for (int g = 0; g < GP; ++g) {
-    s.l[g][rb] ^= s.l[g][ra];
-    s.h[g][rb] ^= s.h[g][ra];
-  }
+  s.l[rb] ^= s.l[ra];
+  s.h[rb] ^= s.h[ra];
 }
 
 // stage-7 butterfly reading the IFFT coefficients c and writing s (stage 7
 // touches every register, so the coset needs no copy of c)
 template <typename T>
 __device__ __forceinline__ void fbfly_from(State &s, const State &c, int ra, int rb, const T &Tb) {
-  s.l[0][ra] = c.l[0][ra];
-  s.h[0][ra] = c.h[0][ra];
-  mul_any(c.l[0][rb], c.h[0][rb], Tb, s.l[0][ra], s.h[0][ra]);
-  s.l[0][rb] = c.l[0][rb] ^ s.l[0][ra];
-  s.h[0][rb] = c.h[0][rb] ^ s.h[0][ra];
+  s.l[ra] = c.l[ra];
+  s.h[ra] = c.h[ra];
+  mul_any(c.l[rb], c.h[rb], Tb, s.l[ra], s.h[ra]);
+  s.l[rb] = c.l[rb] ^ s.l[ra];
+  s.h[rb] = c.h[rb] ^ s.h[ra];
 }
 
 // position held in register r by lane q (0..31) in each layout
@@ -117,14 +106,14 @@ template <Layout FROM, Layout TO>
 __device__ __forceinline__ void exchange(State &s, uint8_t *xch, const XBase &xb) {
 #pragma unroll
   for (int r = 0; r < 8; ++r)
-    *reinterpret_cast<uint2 *>(xch + xcell<FROM>(xb, r)) = make_uint2(s.l[0][r], s.h[0][r]);
+    *reinterpret_cast<uint2 *>(xch + xcell<FROM>(xb, r)) = make_uint2(s.l[r], s.h[r]);
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
     const uint2 v = *reinterpret_cast<const uint2 *>(xch + xcell<TO>(xb, r));
-    s.l[0][r] = v.x;
-    s.h[0][r] = v.y;
+    s.l[r] = v.x;
+    s.h[r] = v.y;
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();

@@ -43,4 +43,8 @@ hipError_t launch_encode_k256w(const CodeParams &p, const DevTables &t, const ui
                   batch, d_shards, sstride, scratch, s, t.cimg);
 }
 
+// the tile counter of the two unpacked k = 256 kernels, encode_k256w (here)
+// and encode_kw<8> (n = 2048, enc_kw.hip): one word on a line of its own
+size_t k256_scratch_bytes(const CodeParams &) { return 256; }
+
 }  // namespace ecamd

@@ -65,7 +65,7 @@ __device__ __forceinline__ void stage_own8(const State &s, uint8_t *xch, uint32_
                                            uint32_t wave) {
 #pragma unroll
   for (int r = 0; r < 8; ++r)
-    *reinterpret_cast<uint2 *>(xch + soff8(posA(q, r), wave) + 8 * inst) = to_be(s.l[0][r], s.h[0][r]);
+    *reinterpret_cast<uint2 *>(xch + soff8(posA(q, r), wave) + 8 * inst) = to_be(s.l[r], s.h[r]);
 }
 
 // the row stores' geometry (enc_w_common.hpp store_own): lane = (row in 8,

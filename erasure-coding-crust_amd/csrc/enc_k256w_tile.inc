@@ -149,7 +149,7 @@
     {  // into tower coordinates
       const TowerK tk = tower_k();
 #pragma unroll
-      for (int r = 0; r < 8; ++r) s.l[0][r] = tower_lo(s.l[0][r], s.h[0][r], tk);
+      for (int r = 0; r < 8; ++r) s.l[r] = tower_lo(s.l[r], s.h[r], tk);
     }
 
     // ---- IFFT_256 (index 0): passes A (bits 0-2), B (3-5), C (6-7)
@@ -170,7 +170,7 @@
       // coef made opaque in place (no copy): keeps the compiler from hoisting
       // the first stage's selector masks out of the coset loop
 #pragma unroll
-      for (int r = 0; r < 8; ++r) asm volatile("" : "+v"(coef.l[0][r]), "+v"(coef.h[0][r]));
+      for (int r = 0; r < 8; ++r) asm volatile("" : "+v"(coef.l[r]), "+v"(coef.h[r]));
       fpassC(s, coef, off);
       rsync();  // previous coset's rows read out
       exchange<LC, LB>(s, xch, xb);
@@ -180,7 +180,7 @@
       {  // back to symbol coordinates
         const TowerK tk = tower_k();
 #pragma unroll
-        for (int r = 0; r < 8; ++r) s.l[0][r] = tower_lo(s.l[0][r], s.h[0][r], tk);
+        for (int r = 0; r < 8; ++r) s.l[r] = tower_lo(s.l[r], s.h[r], tk);
       }
       stage_own8(s, xch, q, inst, wave);
       if constexpr (decltype(last)::value) fetch_next();  // coef and s are dead here

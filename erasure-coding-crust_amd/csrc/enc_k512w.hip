@@ -153,12 +153,12 @@ __device__ __forceinline__ void fpassC9(State &s, const State &c, uint32_t off) 
 __device__ __forceinline__ void swap_c(State &s) {
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    auto l = __builtin_amdgcn_permlane32_swap(s.l[0][r], s.l[0][r + 4], false, false);
-    auto h = __builtin_amdgcn_permlane32_swap(s.h[0][r], s.h[0][r + 4], false, false);
-    s.l[0][r] = l[0];
-    s.l[0][r + 4] = l[1];
-    s.h[0][r] = h[0];
-    s.h[0][r + 4] = h[1];
+    auto l = __builtin_amdgcn_permlane32_swap(s.l[r], s.l[r + 4], false, false);
+    auto h = __builtin_amdgcn_permlane32_swap(s.h[r], s.h[r + 4], false, false);
+    s.l[r] = l[0];
+    s.l[r + 4] = l[1];
+    s.h[r] = h[0];
+    s.h[r + 4] = h[1];
   }
 }
 
@@ -174,7 +174,7 @@ __host__ __device__ constexpr uint32_t soff(uint32_t v, uint32_t w) {
 __device__ __forceinline__ void stage_own(const State &s, uint32_t lane, uint32_t wave) {
   const uint32_t a = XCH0 + wave * XCH_BYTES + soff(8 * lane, wave);
 #pragma unroll
-  for (int r = 0; r < 8; ++r) lds_st2(a ^ soff(uint32_t(r), 0), to_be(s.l[0][r], s.h[0][r]));
+  for (int r = 0; r < 8; ++r) lds_st2(a ^ soff(uint32_t(r), 0), to_be(s.l[r], s.h[r]));
 }
 
 // the row stores' geometry (enc_w_common.hpp store_own): lane = (row in 16,
@@ -351,7 +351,7 @@ __global__ void __launch_bounds__(THREADS, 4) encode_k512w(const uint8_t *__rest
     {  // into tower coordinates
       const TowerK tk = tower_k();
 #pragma unroll
-      for (int r = 0; r < 8; ++r) s.l[0][r] = tower_lo(s.l[0][r], s.h[0][r], tk);
+      for (int r = 0; r < 8; ++r) s.l[r] = tower_lo(s.l[r], s.h[r], tk);
     }
 
     // ---- IFFT_512 (index 0): passes A (bits 0-2), B (3-5), C' (6-8)
@@ -380,7 +380,7 @@ __global__ void __launch_bounds__(THREADS, 4) encode_k512w(const uint8_t *__rest
       uint32_t bA = baseA, bB = baseB;
       asm volatile("" : "+v"(bA), "+v"(bB));
 #pragma unroll
-      for (int r = 0; r < 8; ++r) asm volatile("" : "+v"(coef.l[0][r]), "+v"(coef.h[0][r]));
+      for (int r = 0; r < 8; ++r) asm volatile("" : "+v"(coef.l[r]), "+v"(coef.h[r]));
       fpassC9(s, coef, off);
       swap_c(s);
       ext_ready(j);  // + the previous coset's rows read out of the regions
@@ -391,7 +391,7 @@ __global__ void __launch_bounds__(THREADS, 4) encode_k512w(const uint8_t *__rest
       {  // back to symbol coordinates
         const TowerK tk = tower_k();
 #pragma unroll
-        for (int r = 0; r < 8; ++r) s.l[0][r] = tower_lo(s.l[0][r], s.h[0][r], tk);
+        for (int r = 0; r < 8; ++r) s.l[r] = tower_lo(s.l[r], s.h[r], tk);
       }
       stage_own(s, lane, wave);
     };

@@ -149,7 +149,7 @@ template <int M>
 __device__ __forceinline__ void stage_own(const State &s, uint32_t q, uint32_t g, uint32_t wave) {
   const uint32_t a = XCH0 + wave * XCH_BYTES + soff<M>(8 * q, g, wave);
 #pragma unroll
-  for (int r = 0; r < 8; ++r) lds_st2(a ^ soff<M>(uint32_t(r), 0, 0), to_be(s.l[0][r], s.h[0][r]));
+  for (int r = 0; r < 8; ++r) lds_st2(a ^ soff<M>(uint32_t(r), 0, 0), to_be(s.l[r], s.h[r]));
 }
 
 // the row stores' geometry (enc_w_common.hpp store_own): chunk it * 512 +
@@ -300,7 +300,7 @@ __global__ void __launch_bounds__(THREADS, 4) encode_kw(const uint8_t *__restric
     {  // into tower coordinates
       const TowerK tk = tower_k();
 #pragma unroll
-      for (int r = 0; r < 8; ++r) s.l[0][r] = tower_lo(s.l[0][r], s.h[0][r], tk);
+      for (int r = 0; r < 8; ++r) s.l[r] = tower_lo(s.l[r], s.h[r], tk);
     }
 
     // ---- IFFT_k (index 0): pass A (bits 0-2), then pass B (bits 3..M-1;
@@ -336,7 +336,7 @@ __global__ void __launch_bounds__(THREADS, 4) encode_kw(const uint8_t *__restric
       uint32_t bA = baseA, bB = baseB;
       asm volatile("" : "+v"(bA), "+v"(bB));  // table addresses formed per coset, not hoisted
 #pragma unroll
-      for (int r = 0; r < 8; ++r) asm volatile("" : "+v"(coef.l[0][r]), "+v"(coef.h[0][r]));
+      for (int r = 0; r < 8; ++r) asm volatile("" : "+v"(coef.l[r]), "+v"(coef.h[r]));
       if constexpr (M == 8) {
         fpassC(s, coef, off);
         // previous coset's rows read out; from coset 4 on, also this coset's
@@ -366,7 +366,7 @@ __global__ void __launch_bounds__(THREADS, 4) encode_kw(const uint8_t *__restric
       {  // back to symbol coordinates
         const TowerK tk = tower_k();
 #pragma unroll
-        for (int r = 0; r < 8; ++r) s.l[0][r] = tower_lo(s.l[0][r], s.h[0][r], tk);
+        for (int r = 0; r < 8; ++r) s.l[r] = tower_lo(s.l[r], s.h[r], tk);
       }
       stage_own<M>(s, q, g, wave);
     };

@@ -174,14 +174,14 @@ template <Layout FROM, Layout TO>
 __device__ __forceinline__ void xchg(State &s, XBase xb) {
   asm volatile("" : "+v"(xb.a), "+v"(xb.b), "+v"(xb.c));
 #pragma unroll
-  for (int r = 0; r < 8; ++r) lds_st2(xcell<FROM>(xb, r), make_uint2(s.l[0][r], s.h[0][r]));
+  for (int r = 0; r < 8; ++r) lds_st2(xcell<FROM>(xb, r), make_uint2(s.l[r], s.h[r]));
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
     const uint2 v = lds_ld2(xcell<TO>(xb, r));
-    s.l[0][r] = v.x;
-    s.h[0][r] = v.y;
+    s.l[r] = v.x;
+    s.h[r] = v.y;
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -232,10 +232,10 @@ __device__ __forceinline__ void to_state(const v4u (&d)[4], State &s) {
     const uint32_t D0 = d[0][j], D1 = d[1][j], D2 = d[2][j], D3 = d[3][j];
     const uint32_t t0 = vperm(D1, D0, 0x05010400u), t1 = vperm(D1, D0, 0x07030602u);
     const uint32_t u0 = vperm(D3, D2, 0x05010400u), u1 = vperm(D3, D2, 0x07030602u);
-    s.h[0][2 * j] = vperm(u0, t0, 0x05040100u);
-    s.l[0][2 * j] = vperm(u0, t0, 0x07060302u);
-    s.h[0][2 * j + 1] = vperm(u1, t1, 0x05040100u);
-    s.l[0][2 * j + 1] = vperm(u1, t1, 0x07060302u);
+    s.h[2 * j] = vperm(u0, t0, 0x05040100u);
+    s.l[2 * j] = vperm(u0, t0, 0x07060302u);
+    s.h[2 * j + 1] = vperm(u1, t1, 0x05040100u);
+    s.l[2 * j + 1] = vperm(u1, t1, 0x07060302u);
   }
 }
 

@@ -118,9 +118,8 @@ for k in kinds:
         # line serialise in L2: ~6 ns per atomic); 1152 B of scratch, zeroed by
         # the shared launch tail: every kernel launched through it gets them
         com = rep(com, "launch_zero_counters(tick, sizeof(uint32_t), s)", "launch_zero_counters(tick, 1152, s)")
-        extra["enc_k256.hip"] = rep(open(f"{CS}/enc_k256.hip").read(),
-                                    "size_t k256_scratch_bytes(const CodeParams &) { return 256; }",
-                                    "size_t k256_scratch_bytes(const CodeParams &) { return 1152; }")
+        enc = rep(enc, "size_t k256_scratch_bytes(const CodeParams &) { return 256; }",
+                  "size_t k256_scratch_bytes(const CodeParams &) { return 1152; }")
         extra["enc_kw.hip"] = rep(open(f"{CS}/enc_kw.hip").read(), "kw_applicable(p) ? 256 : 0", "kw_applicable(p) ? 1152 : 0")
         extra["enc_k512w.hip"] = rep(open(f"{CS}/enc_k512w.hip").read(), "k512w_applicable(p) ? 256 : 0",
                                      "k512w_applicable(p) ? 1152 : 0")

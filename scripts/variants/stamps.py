@@ -2,7 +2,10 @@
 """Diagnostic variants with per-phase s_memtime stamps (results unchanged; the
 product sources carry no switches: this script writes patched copies).
 
-  stamps.py enc OUT.hip   encode_k256: load / barrier wait / row stores / compute
+  stamps.py enc OUT.hip   the packed encode_k256 (enc_k256.hip): load / barrier
+                          wait / row stores / compute; the barrier stamps are
+                          in the workgroup-barrier arm of rsync, so they count
+                          for encode_k256<2048, 1> only (<1024, 2> has none)
   stamps.py dec OUT.hip   reconstruct_n1024: gather / barrier waits / IFFT /
                           derivative+FFT / output
 
@@ -65,8 +68,8 @@ if kind == "enc":
 elif kind == "dec":
     s = open(f"{ROOT}/erasure-coding-crust_amd/csrc/dec_n1024.hip").read()
     s = rep(s, "namespace ecamd {\nnamespace {", "namespace ecamd {\n__device__ unsigned long long g_stamp[16];\nnamespace {")
-    s = rep(s, "  Tabs::copy_image<THREADS>(tabs, kF9 ? t.timg_f9 : t.timg_t, tid0);  // F9 kind 0\n  __syncthreads();\n",
-            "  Tabs::copy_image<THREADS>(tabs, kF9 ? t.timg_f9 : t.timg_t, tid0);  // F9 kind 0\n  __syncthreads();\n" + STAMP)
+    s = rep(s, "  Tabs::copy_image<THREADS>(tabs, t.timg_f9, tid0);  // F9 kind 0\n  __syncthreads();\n",
+            "  Tabs::copy_image<THREADS>(tabs, t.timg_f9, tid0);  // F9 kind 0\n  __syncthreads();\n" + STAMP)
     s = rep(s, "    if ((meta[0] & 0xffffu) != 0xffffu) load_row(0);\n    lds_barrier();",
             "    if ((meta[0] & 0xffffu) != 0xffffu) load_row(0);\n    STAMP(0);\n    lds_barrier();\n    STAMP(1);")
     s = rep(s, "    if constexpr (!PACKED) __syncthreads();  // packed",

@@ -1226,7 +1226,11 @@ def test_fresh_process_concurrent_first_calls():
     (1024, 5000, 40, "tight"), (1024, 5000, 24, "pad64"), (1024, 16385, 5, "odd"), (1024, 65535, 3, "tight"),
     (1024, 70001, 3, "odd"),                     # > 64 KB with odd pitches: packed tiles too
     (800, 300, 45, "tight"), (1000, 20000, 7, "pad16"), (766, 15, 80, "odd"),
-    (1025, 300, 31, "tight"), (1500, 5000, 9, "odd")])  # n = 2048 encode (packed) / reconstruct_n4096
+    (1025, 300, 31, "tight"), (1500, 5000, 9, "odd"),  # n = 2048 encode (packed) / reconstruct_n4096
+    # encode_k256<2048, 1>: 16 slots a payload, 432 slots = three whole 128-slot tiles and a partial
+    # one, five cosets (table image 1 reloaded at 1024); <1024, 2>: 26 pieces = three whole wave
+    # tasks and a partial one, a payload's two pieces in different tasks
+    (1533, 5000, 27, "pitch+1"), (1024, 513, 13, "pitch+2")])
 def test_packed_small_batches(oracle, nv, plen, batch, layout):
     """Small payloads (the benchmark/ sizes) and pitches the 16-B kernels cannot
     take run the packed encode_k256 / reconstruct_n1024 (flattened pieces /
@@ -1234,7 +1238,8 @@ def test_packed_small_batches(oracle, nv, plen, batch, layout):
     byte vs the oracle, shard rows and outputs prefilled with 0xAA (a write
     past a payload's pieces or columns shows up), absent rows overwritten with
     garbage.  tight: pitch = length; odd: odd payload base and pitch, shard
-    pitch = shard_len + 2; padNN: pitches rounded to NN bytes."""
+    pitch = shard_len + 2; padNN: pitches rounded to NN bytes; pitch+N: payload
+    pitch = length + N, tight (even) shard pitch."""
     import torch
     n, k, thr = E.code_params(nv)
     sl = E.shard_len(nv, plen)
@@ -1242,6 +1247,8 @@ def test_packed_small_batches(oracle, nv, plen, batch, layout):
         ps, ss, off = plen, sl, 0
     elif layout == "odd":
         ps, ss, off = plen + 3, sl + 2, 1
+    elif layout.startswith("pitch+"):
+        ps, ss, off = plen + int(layout[6:]), sl, 0
     else:
         pad = int(layout[3:])
         ps, ss, off = (plen + pad - 1) // pad * pad, (sl + pad - 1) // pad * pad, 0
@@ -1253,6 +1260,7 @@ def test_packed_small_batches(oracle, nv, plen, batch, layout):
     d_buf = torch.from_numpy(buf).cuda()
     d_pay = d_buf[off:]
     d_sh = _prefilled((batch * nv * ss,))
+    assert E.encode_kernel(nv, d_pay, plen, ps, batch, d_sh, ss) == "encode_k256_packed"
     E.encode_batch(nv, d_pay, plen, ps, batch, d_sh, ss)
     torch.cuda.synchronize()
     shv = d_sh.cpu().numpy().reshape(batch, nv, ss)
