@@ -39,12 +39,22 @@
  * payloads of unequal length see "ragged batches" below):
  *   payloads   : [batch][payload_stride] bytes, payload_len used
  *   shards     : [batch][n_validators][shard_stride] bytes, shard_len used
- *   present    : [batch][n] bytes, 1 = shard present (indices >= n_validators
- *                are always treated as erased)
+ *   present    : [batch][n] bytes, any non-zero byte = shard present, 0 =
+ *                erased (indices >= n_validators are always treated as
+ *                erased, whatever their bytes)
  *   err_log    : [batch][n] uint16 log-domain erasure-locator multipliers
- *                (poly_encoder.hpp:90-116), produced by ECCR_AMD_error_locator
+ *                (poly_encoder.hpp:90-116), produced by ECCR_AMD_error_locator.
+ *                The values are logs mod 65535: 0 and 65535 both mean
+ *                "multiply by one", a row produced by the locator may hold
+ *                either, and the reconstruct calls take both.  Only the
+ *                entries of present rows and of erased rows below k enter the
+ *                result (decode_main, poly_encoder.hpp:174-188): entries at
+ *                erased rows >= k and at rows >= n_validators may hold
+ *                anything
  *   out        : [batch][out_stride] bytes, shard_len * k used (zero-padded
  *                past payload_len, as the reference)
+ * (tests/test_locator_contract.py pins the present / err_log rules on every
+ * reconstruct kernel.)
  */
 #ifndef ERASURE_CODING_EC_AMD_H_
 #define ERASURE_CODING_EC_AMD_H_
