@@ -30,42 +30,11 @@ using OutTabs = LdsTabs<128>;  // E[y], y < k <= 128, own area: filled once per 
 constexpr int LDS_BYTES = Tabs::kBytes + WAVES * REG_BYTES + OutTabs::kBytes;
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 
-// inverse pass over register bits 0..NS-1 (position bits B0..) of
-// the local index pos & (n - 1); lb = tlin of the (masked) lane part
-// When the pass holds the top local bit (B0 + NS == L), the lane part of a
-// skew index has no bits above the stage, so a register block whose bits above
-// the stage are 0 (blk < 2d) has skew skews[d - 1] = 0xFFFF: b ^= a only.
 // Tower image 0: stages >= SM multiply with subfield tables.
+// The inverse passes are tf::ipass4<B0, SM, false, NS, L>: register bits
+// 0..NS-1 (position bits B0..) of the local index pos & (n - 1), lb = tlin of
+// the (masked) lane part.
 constexpr int SM = tower_sub_min(0);
-template <int B0, int NS, int L>
-__device__ __forceinline__ void ipassg(S16 &s, const uint8_t *tabs, uint32_t lb) {
-  constexpr uint32_t NM = (1u << L) - 1;
-  constexpr bool TOP = B0 + NS == L;
-  Tab T[2];
-  SubTab U[2];
-  const auto fetch = [&](int t, int blk, int slot) __attribute__((always_inline)) {
-    const uint32_t a = lb ^ tlin(skew_idx((uint32_t(blk) << B0) & NM, B0 + t));
-    if (B0 + t >= SM) tab_at(tabs, a, U[slot]);
-    else tab_at(tabs, a, T[slot]);
-  };
-  fetch(0, 0, 0);
-  int k = 0;
-#pragma unroll
-  for (int t = 0; t < NS; ++t) {
-    const int d = 1 << t;
-#pragma unroll
-    for (int blk = 0; blk < 16; blk += 2 * d, ++k) {
-      const int nt = blk + 2 * d < 16 ? t : t + 1, nblk = blk + 2 * d < 16 ? blk + 2 * d : 0;
-      if (nt < NS) fetch(nt, nblk, (k + 1) & 1);
-#pragma unroll
-      for (int i = 0; i < d; ++i) {
-        if (TOP && ((blk << B0) & NM) >> (B0 + t + 1) == 0) bx(s, blk + i, blk + i + d);
-        else if (B0 + t >= SM) ib(s, blk + i, blk + i + d, U[k & 1]);
-        else ib(s, blk + i, blk + i + d, T[k & 1]);
-      }
-    }
-  }
-}
 
 // layout C, L = 9 or 10: stage 8 (pairs r bit 0, skew by p9 when local) and
 // stage 9 (L = 10).  The transform is at index 0, so a stage's block at j = d
@@ -254,19 +223,19 @@ __global__ void __launch_bounds__(THREADS) reconstruct_gen(
     // priority (pass A: w + 4, then w), as in reconstruct_n1024
     if (wave & 4) __builtin_amdgcn_s_setprio(2);
     else __builtin_amdgcn_s_setprio(0);
-    ipassg<0, 4, L>(s, tabs, lbA());
+    ipass4<0, SM, false, 4, L>(s, tabs, lbA());
     __builtin_amdgcn_sched_barrier(0);
     if (wave & 4) __builtin_amdgcn_s_setprio(0);
     else __builtin_amdgcn_s_setprio(2);
     exchange<LA, LB>(s, my, lane);
     if constexpr (L <= 8) {
-      ipassg<4, L - 4, L>(s, tabs, lbB());
+      ipass4<4, SM, false, L - 4, L>(s, tabs, lbB());
       __builtin_amdgcn_sched_barrier(0);
       derivative<LB, L, KB>(s, lane);
       __builtin_amdgcn_sched_barrier(0);
       fft_restricted<LB, L, KB, SM>(s, tabs, lane);
     } else {
-      ipassg<4, 4, L>(s, tabs, lbB());
+      ipass4<4, SM, false, 4, L>(s, tabs, lbB());
       __builtin_amdgcn_sched_barrier(0);
       exchange<LB, LC>(s, my, lane);
       ipassCg<L>(s, tabs);

@@ -371,7 +371,7 @@ __global__ void __launch_bounds__(THREADS) reconstruct_n1024(
         s.h[r] = x.y;
       }
       prio_lead(wave_s & 4);
-      ipass4<0>(s, tabs, tlin(16 * lane));
+      ipass4<0, SUB, true>(s, Lds0{}, tlin(16 * lane));
 #pragma unroll
       for (int r = 0; r < 16; ++r) lds_st2(la ^ raddr(r), make_uint2(s.l[r], s.h[r]));
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -387,7 +387,7 @@ __global__ void __launch_bounds__(THREADS) reconstruct_n1024(
         s.h[r] = x.y;
       }
       prio_lead(!(wave_s & 4));
-      ipass4<4>(s, tabs, tlin((lane >> 4) << 8));
+      ipass4<4, SUB, true>(s, Lds0{}, tlin((lane >> 4) << 8));
 #pragma unroll
       for (int r = 0; r < 16; ++r) lds_st2(lb ^ raddr(uint32_t(r) << 4), make_uint2(s.l[r], s.h[r]));
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -407,7 +407,7 @@ __global__ void __launch_bounds__(THREADS) reconstruct_n1024(
     // p8 = p9 = 1 registers (4 hi + 3) are not needed past stage 8.
     {
       SubTab Tb;
-      tab_at(tabs, tlin(skew_idx(1u << 9, 8)), Tb);
+      tab_at(Lds0{}, tlin(skew_idx(1u << 9, 8)), Tb);
 #pragma unroll
       for (int hi = 0; hi < 4; ++hi) {
         s.l[4 * hi + 1] ^= s.l[4 * hi];  // stage 8, p9 = 0 block
@@ -423,142 +423,32 @@ __global__ void __launch_bounds__(THREADS) reconstruct_n1024(
     }
 
     prio_lead(wave_s & 4);
-    // ---- phases 3 + 4a: formal derivative (poly_encoder.hpp:195-215) and FFT
-    // stages 9, 8 (afft, additive_fft.hpp:121-141) for the outputs y < 256 only.
-    // Those FFT stages keep the block at j = d, whose skew skews[d - 1] is
-    // 0xFFFF: a ^= b * skew is a no-op, so they pass c'[y] through for y < 256,
-    // and the derivative is needed at y < 256 only.  Its closed form
-    // c'[y] = c[y] ^ XOR_{b: y_b = 0} c[y | 2^b] there reads
-    //   c'[y] = c0[y] ^ c1[y] ^ c2[y] ^ XOR_{b < 8, y_b = 0} c0[y | 2^b]
-    // with c0 / c1 / c2 = registers 4 q / 4 q + 1 / 4 q + 2 (p8 p9 = 00 / 10 /
-    // 01), q bit 0 = p6, bit 1 = p7, lane bits = p0..p5.
-    // Lane-bit terms (lanes with p_b = 0 add the value of lane + 2^b): p2, p3
-    // by one row_shl DPP xor each whose bank mask leaves the p_b = 1 lanes
-    // untouched; p0, p1 by quad_perm DPP xors that hand the p_b = 1 lanes
-    // their own c0 instead of 0 (corrected once: c0 is kept where p0 ^ p1 = 0
-    // rather than xor'ed twice); p4, p5 by permlane swaps, masked.
-    uint32_t ql[4], qh[4];
-    {
-      const uint32_t keep0 = ((lane ^ (lane >> 1)) & 1) ? 0u : 0xffffffffu;
-      const uint32_t m4 = ((lane >> 4) & 1) ? 0u : 0xffffffffu;
-      const uint32_t m5 = ((lane >> 5) & 1) ? 0u : 0xffffffffu;
-      const auto lane_terms = [&](uint32_t c0, uint32_t acc) {
-        acc ^= uint32_t(__builtin_amdgcn_update_dpp(0, int(c0), 0xF5, 0xf, 0xf, false));  // quad [1,1,3,3]
-        acc ^= uint32_t(__builtin_amdgcn_update_dpp(0, int(c0), 0xEE, 0xf, 0xf, false));  // quad [2,3,2,3]
-        acc ^= uint32_t(__builtin_amdgcn_update_dpp(0, int(c0), 0x104, 0xf, 0x5, false));  // row_shl:4, banks 0, 2
-        acc ^= uint32_t(__builtin_amdgcn_update_dpp(0, int(c0), 0x108, 0xf, 0x3, false));  // row_shl:8, banks 0, 1
-        acc = __builtin_amdgcn_bitop3_b32(acc, from_upper(c0, 4), m4, 0x78);  // acc ^ (x & m)
-        acc = __builtin_amdgcn_bitop3_b32(acc, from_upper(c0, 5), m5, 0x78);
-        return __builtin_amdgcn_bitop3_b32(acc, c0, keep0, 0x78);
-      };
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        uint32_t al = s.l[4 * q + 1] ^ s.l[4 * q + 2], ah = s.h[4 * q + 1] ^ s.h[4 * q + 2];
-        if (!(q & 1)) {  // p6 = 0
-          al ^= s.l[4 * (q | 1)];
-          ah ^= s.h[4 * (q | 1)];
-        }
-        if (!(q & 2)) {  // p7 = 0
-          al ^= s.l[4 * (q | 2)];
-          ah ^= s.h[4 * (q | 2)];
-        }
-        ql[q] = lane_terms(s.l[4 * q], al);
-        qh[q] = lane_terms(s.h[4 * q], ah);
+    // ---- phases 3 + 4a and the rest of 4: the closed-form derivative at
+    // y < 256 and the FFT restricted to y < 256, dec_n1024_dfft.inc (one copy,
+    // shared with reconstruct_n1024x).  Table addresses in order of use (lane
+    // bits after each of its swap stages):
+    const uint32_t hi67 = ((lane >> 4) & 3) << 6, lo = lane & 15;
+    const uint32_t hi47 = ((lane >> 2) & 15) << 4, lo01 = lane & 3;
+    const uint32_t hi27 = lane << 2;
+    auto L = [&](int i) -> uint32_t {
+      switch (i) {
+        case 2: return tlin(skew_idx(1u << 7, 6));
+        case 3: return tlin(skew_idx(hi67 | lo, 5));
+        case 4: return tlin(skew_idx(hi67 | lo, 4));
+        case 5: return tlin(skew_idx(hi67 | 32u | lo, 4));
+        case 6: return tlin(skew_idx(hi47 | lo01, 3));
+        case 7: return tlin(skew_idx(hi47 | lo01, 2));
+        case 8: return tlin(skew_idx(hi47 | 8u | lo01, 2));
+        // stages 1, 0: their image slots hold general tables; the stage-2
+        // slot of the same (subfield) skew element instead (sub_alias)
+        case 9: return tlin(sub_alias(hi27, 1));
+        case 10: return tlin(sub_alias(hi27, 0));
+        default: return tlin(sub_alias(hi27 | 2u, 0));
       }
-    }
-    {
-      // q bit0 = p6, bit1 = p7; lane bits = p0..p5.  Positions < 256 only.
-      auto fb = [&](int a, int bb, const SubTab &T) {  // every stage >= SUB for y < 256
-        mul_acc_sub(ql[bb], qh[bb], T, ql[a], qh[a]);
-        ql[bb] ^= ql[a];
-        qh[bb] ^= qh[a];
-      };
-      // table addresses in order of use (lane bits after each swap stage below)
-      const uint32_t hi67 = ((lane >> 4) & 3) << 6, lo = lane & 15;
-      const uint32_t hi47 = ((lane >> 2) & 15) << 4, lo01 = lane & 3;
-      const uint32_t hi27 = lane << 2;
-      auto L = [&](int i) -> uint32_t {
-        switch (i) {
-          case 2: return tlin(skew_idx(1u << 7, 6));
-          case 3: return tlin(skew_idx(hi67 | lo, 5));
-          case 4: return tlin(skew_idx(hi67 | lo, 4));
-          case 5: return tlin(skew_idx(hi67 | 32u | lo, 4));
-          case 6: return tlin(skew_idx(hi47 | lo01, 3));
-          case 7: return tlin(skew_idx(hi47 | lo01, 2));
-          case 8: return tlin(skew_idx(hi47 | 8u | lo01, 2));
-          // stages 1, 0: their image slots hold general tables; the stage-2
-          // slot of the same (subfield) skew element instead (sub_alias)
-          case 9: return tlin(sub_alias(hi27, 1));
-          case 10: return tlin(sub_alias(hi27, 0));
-          default: return tlin(sub_alias(hi27 | 2u, 0));
-        }
-      };
-      // stage 7 (block j = 128) and stage 6's first block (j = 64) have the
-      // skew 0xFFFF at index 0 (additive_fft.hpp:129): b ^= a only
-      const auto fx = [&](int a, int bb) {
-        ql[bb] ^= ql[a];
-        qh[bb] ^= qh[a];
-      };
-      SubTab T[2];
-      tab_at(tabs, L(2), T[0]);
-      tab_at(tabs, L(3), T[1]);
-      fx(0, 2);  // stage 7
-      fx(1, 3);
-      fx(0, 1);  // stage 6
-      fb(2, 3, T[0]);
-      tab_at(tabs, L(4), T[0]);
-      // q (p6, p7) <-> lane bits 4, 5 (p4, p5)
-      swap_bit(ql[0], ql[1], 4, false);
-      swap_bit(qh[0], qh[1], 4, false);
-      swap_bit(ql[2], ql[3], 4, false);
-      swap_bit(qh[2], qh[3], 4, false);
-      swap_bit(ql[0], ql[2], 5, false);
-      swap_bit(qh[0], qh[2], 5, false);
-      swap_bit(ql[1], ql[3], 5, false);
-      swap_bit(qh[1], qh[3], 5, false);
-      // now q = (p4, p5); lane bits 0-3 = p0..p3, 4 = p6, 5 = p7
-      fb(0, 2, T[1]);  // stage 5
-      fb(1, 3, T[1]);
-      tab_at(tabs, L(5), T[1]);
-      fb(0, 1, T[0]);  // stage 4
-      tab_at(tabs, L(6), T[0]);
-      fb(2, 3, T[1]);
-      tab_at(tabs, L(7), T[1]);
-      // q (p4, p5) <-> lane bits 2, 3 (p2, p3)
-      const bool l2 = (lane >> 2) & 1, l3 = (lane >> 3) & 1;
-      swap_bit(ql[0], ql[1], 2, l2);
-      swap_bit(qh[0], qh[1], 2, l2);
-      swap_bit(ql[2], ql[3], 2, l2);
-      swap_bit(qh[2], qh[3], 2, l2);
-      swap_bit(ql[0], ql[2], 3, l3);
-      swap_bit(qh[0], qh[2], 3, l3);
-      swap_bit(ql[1], ql[3], 3, l3);
-      swap_bit(qh[1], qh[3], 3, l3);
-      // now q = (p2, p3); lane bits 0,1 = p0,p1; 2,3 = p4,p5; 4,5 = p6,p7
-      fb(0, 2, T[0]);  // stage 3
-      fb(1, 3, T[0]);
-      tab_at(tabs, L(8), T[0]);
-      fb(0, 1, T[1]);  // stage 2
-      tab_at(tabs, L(9), T[1]);
-      fb(2, 3, T[0]);
-      tab_at(tabs, L(10), T[0]);
-      // q (p2, p3) <-> lane bits 0, 1 (p0, p1)
-      const bool l0 = lane & 1, l1 = (lane >> 1) & 1;
-      swap_bit(ql[0], ql[1], 0, l0);
-      swap_bit(qh[0], qh[1], 0, l0);
-      swap_bit(ql[2], ql[3], 0, l0);
-      swap_bit(qh[2], qh[3], 0, l0);
-      swap_bit(ql[0], ql[2], 1, l1);
-      swap_bit(qh[0], qh[2], 1, l1);
-      swap_bit(ql[1], ql[3], 1, l1);
-      swap_bit(qh[1], qh[3], 1, l1);
-      // now q = (p0, p1); lane = (p2 .. p7): y = 4 * lane + q
-      fb(0, 2, T[1]);  // stage 1
-      fb(1, 3, T[1]);
-      tab_at(tabs, L(11), T[1]);
-      fb(0, 1, T[0]);  // stage 0
-      fb(2, 3, T[1]);
-    }
+    };
+#define DFFT_TAB(i, T) tab_at(Lds0{}, L(i), T)
+#include "dec_n1024_dfft.inc"
+#undef DFFT_TAB
     // the output at equal priority (round 4: 11.00-11.03 against 11.05 ms with
     // w leading, which round 3 measured as the better one, 11.26 -> 11.19)
     __builtin_amdgcn_s_setprio(0);
@@ -591,17 +481,7 @@ __global__ void __launch_bounds__(THREADS) reconstruct_n1024(
           ol[q] = vperm(rc[q], ra[q], 0x07050301u);
         }
       }
-      // column c of the group: 4 consecutive y -> 8 bytes BE
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const uint64_t col = cbase + c;
-        if (col >= ncols) break;
-        const uint32_t w0 = vperm(ol[0], oh[0], 0x0c0c0400u + 0x0101u * c) |
-                            (vperm(ol[1], oh[1], 0x0c0c0400u + 0x0101u * c) << 16);
-        const uint32_t w1 = vperm(ol[2], oh[2], 0x0c0c0400u + 0x0101u * c) |
-                            (vperm(ol[3], oh[3], 0x0c0c0400u + 0x0101u * c) << 16);
-        *reinterpret_cast<uint2 *>(O + (col * K + 4 * lane) * 2) = make_uint2(w0, w1);
-      }
+#include "dec_n1024_store.inc"
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) meta[i] = meta_next[i];

@@ -77,8 +77,8 @@ __device__ __forceinline__ uint32_t stg_row(uint32_t y) {
 
 // Region address of position v (8-byte cells, GF(2)-linear): conflict-free
 // for the reads (2 x 32 lanes) and writes (4 x 16 lanes) of the three layouts
-// below (scripts/search_raddr.py's condition; raddr, dec_n1024_common.hpp,
-// is 2-way on layout A' reads)
+// below (scripts/search_raddr.py's condition; raddr, tf1024.hpp, is 2-way on
+// layout A' reads)
 __host__ __device__ constexpr uint32_t rz(uint32_t v) {
   return ((v >> 5) << 8) | (((v ^ (v >> 4) ^ (v >> 5)) & 31) << 3);
 }
@@ -166,10 +166,6 @@ __device__ __forceinline__ void ipassB2(S16 &s, uint32_t lane) {
 // IFFT stages 6-9 in layout C (r bit 0 = p8, 1 = p9, 2 = p6, 3 = p7): the
 // elements are wave-uniform (broadcast table reads); x = 0 is b ^= a only
 // (the skew 0xFFFF, additive_fft.hpp:110-112)
-__device__ __forceinline__ void bx(S16 &s, int a, int b) {
-  s.l[b] ^= s.l[a];
-  s.h[b] ^= s.h[a];
-}
 __device__ __forceinline__ void ipassC2(S16 &s) {
   SubTab X1, X2, X3, X4;
   ctab(0u, cimg_lin(1), X1);

@@ -231,118 +231,29 @@
     }
 
     // ---- phases 3 + 4: the closed-form derivative at y < 256 and the FFT
-    // restricted to y < 256 (dec_n1024.hip, the same steps)
-    uint32_t ql[4], qh[4];
-    {
-      const uint32_t keep0 = ((lane ^ (lane >> 1)) & 1) ? 0u : 0xffffffffu;
-      const uint32_t m4 = ((lane >> 4) & 1) ? 0u : 0xffffffffu;
-      const uint32_t m5 = ((lane >> 5) & 1) ? 0u : 0xffffffffu;
-      const auto lane_terms = [&](uint32_t c0, uint32_t acc) {
-        acc ^= uint32_t(__builtin_amdgcn_update_dpp(0, int(c0), 0xF5, 0xf, 0xf, false));  // quad [1,1,3,3]
-        acc ^= uint32_t(__builtin_amdgcn_update_dpp(0, int(c0), 0xEE, 0xf, 0xf, false));  // quad [2,3,2,3]
-        acc ^= uint32_t(__builtin_amdgcn_update_dpp(0, int(c0), 0x104, 0xf, 0x5, false));  // row_shl:4, banks 0, 2
-        acc ^= uint32_t(__builtin_amdgcn_update_dpp(0, int(c0), 0x108, 0xf, 0x3, false));  // row_shl:8, banks 0, 1
-        acc = __builtin_amdgcn_bitop3_b32(acc, from_upper(c0, 4), m4, 0x78);  // acc ^ (x & m)
-        acc = __builtin_amdgcn_bitop3_b32(acc, from_upper(c0, 5), m5, 0x78);
-        return __builtin_amdgcn_bitop3_b32(acc, c0, keep0, 0x78);
-      };
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        uint32_t al = s.l[4 * q + 1] ^ s.l[4 * q + 2], ah = s.h[4 * q + 1] ^ s.h[4 * q + 2];
-        if (!(q & 1)) {  // p6 = 0
-          al ^= s.l[4 * (q | 1)];
-          ah ^= s.h[4 * (q | 1)];
-        }
-        if (!(q & 2)) {  // p7 = 0
-          al ^= s.l[4 * (q | 2)];
-          ah ^= s.h[4 * (q | 2)];
-        }
-        ql[q] = lane_terms(s.l[4 * q], al);
-        qh[q] = lane_terms(s.h[4 * q], ah);
+    // restricted to y < 256, dec_n1024_dfft.inc (one copy, shared with
+    // reconstruct_n1024); the table of its step i is at L(i)
+    const uint32_t hi67 = ((lane >> 4) & 3) << 6, lo = lane & 15;
+    const uint32_t hi47 = ((lane >> 2) & 15) << 4, lo01 = lane & 3;
+    const uint32_t hi27 = lane << 2;
+    // the restricted FFT's elements x = pos >> (m + 1) (compact image entries)
+    auto L = [&](int i) -> uint32_t {
+      switch (i) {
+        case 2: return cimg_lin(1);                         // stage 6, p7 = 1
+        case 3: return cimg_lin((hi67 | lo) >> 6);          // stage 5
+        case 4: return cimg_lin((hi67 | lo) >> 5);          // stage 4
+        case 5: return cimg_lin((hi67 | 32u | lo) >> 5);
+        case 6: return cimg_lin((hi47 | lo01) >> 4);        // stage 3
+        case 7: return cimg_lin((hi47 | lo01) >> 3);        // stage 2
+        case 8: return cimg_lin((hi47 | 8u | lo01) >> 3);
+        case 9: return cimg_lin(hi27 >> 2);                 // stage 1
+        case 10: return cimg_lin(hi27 >> 1);                // stage 0
+        default: return cimg_lin((hi27 | 2u) >> 1);
       }
-    }
-    {
-      auto fb = [&](int a, int bb, const SubTab &T) {  // every stage >= SUB for y < 256
-        mul_acc_sub(ql[bb], qh[bb], T, ql[a], qh[a]);
-        ql[bb] ^= ql[a];
-        qh[bb] ^= qh[a];
-      };
-      const uint32_t hi67 = ((lane >> 4) & 3) << 6, lo = lane & 15;
-      const uint32_t hi47 = ((lane >> 2) & 15) << 4, lo01 = lane & 3;
-      const uint32_t hi27 = lane << 2;
-      // the restricted FFT's elements x = pos >> (m + 1) (compact image entries)
-      auto L = [&](int i) -> uint32_t {
-        switch (i) {
-          case 2: return cimg_lin(1);                         // stage 6, p7 = 1
-          case 3: return cimg_lin((hi67 | lo) >> 6);          // stage 5
-          case 4: return cimg_lin((hi67 | lo) >> 5);          // stage 4
-          case 5: return cimg_lin((hi67 | 32u | lo) >> 5);
-          case 6: return cimg_lin((hi47 | lo01) >> 4);        // stage 3
-          case 7: return cimg_lin((hi47 | lo01) >> 3);        // stage 2
-          case 8: return cimg_lin((hi47 | 8u | lo01) >> 3);
-          case 9: return cimg_lin(hi27 >> 2);                 // stage 1
-          case 10: return cimg_lin(hi27 >> 1);                // stage 0
-          default: return cimg_lin((hi27 | 2u) >> 1);
-        }
-      };
-      const auto fx = [&](int a, int bb) {
-        ql[bb] ^= ql[a];
-        qh[bb] ^= qh[a];
-      };
-      SubTab T[2];
-      ctab(0u, L(2), T[0]);
-      ctab(0u, L(3), T[1]);
-      fx(0, 2);  // stage 7
-      fx(1, 3);
-      fx(0, 1);  // stage 6
-      fb(2, 3, T[0]);
-      ctab(0u, L(4), T[0]);
-      swap_bit(ql[0], ql[1], 4, false);
-      swap_bit(qh[0], qh[1], 4, false);
-      swap_bit(ql[2], ql[3], 4, false);
-      swap_bit(qh[2], qh[3], 4, false);
-      swap_bit(ql[0], ql[2], 5, false);
-      swap_bit(qh[0], qh[2], 5, false);
-      swap_bit(ql[1], ql[3], 5, false);
-      swap_bit(qh[1], qh[3], 5, false);
-      fb(0, 2, T[1]);  // stage 5
-      fb(1, 3, T[1]);
-      ctab(0u, L(5), T[1]);
-      fb(0, 1, T[0]);  // stage 4
-      ctab(0u, L(6), T[0]);
-      fb(2, 3, T[1]);
-      ctab(0u, L(7), T[1]);
-      const bool l2 = (lane >> 2) & 1, l3 = (lane >> 3) & 1;
-      swap_bit(ql[0], ql[1], 2, l2);
-      swap_bit(qh[0], qh[1], 2, l2);
-      swap_bit(ql[2], ql[3], 2, l2);
-      swap_bit(qh[2], qh[3], 2, l2);
-      swap_bit(ql[0], ql[2], 3, l3);
-      swap_bit(qh[0], qh[2], 3, l3);
-      swap_bit(ql[1], ql[3], 3, l3);
-      swap_bit(qh[1], qh[3], 3, l3);
-      fb(0, 2, T[0]);  // stage 3
-      fb(1, 3, T[0]);
-      ctab(0u, L(8), T[0]);
-      fb(0, 1, T[1]);  // stage 2
-      ctab(0u, L(9), T[1]);
-      fb(2, 3, T[0]);
-      ctab(0u, L(10), T[0]);
-      const bool l0 = lane & 1, l1 = (lane >> 1) & 1;
-      swap_bit(ql[0], ql[1], 0, l0);
-      swap_bit(qh[0], qh[1], 0, l0);
-      swap_bit(ql[2], ql[3], 0, l0);
-      swap_bit(qh[2], qh[3], 0, l0);
-      swap_bit(ql[0], ql[2], 1, l1);
-      swap_bit(qh[0], qh[2], 1, l1);
-      swap_bit(ql[1], ql[3], 1, l1);
-      swap_bit(qh[1], qh[3], 1, l1);
-      fb(0, 2, T[1]);  // stage 1
-      fb(1, 3, T[1]);
-      ctab(0u, L(11), T[1]);
-      fb(0, 1, T[0]);  // stage 0
-      fb(2, 3, T[1]);
-    }
+    };
+#define DFFT_TAB(i, T) ctab(0u, L(i), T)
+#include "dec_n1024_dfft.inc"
+#undef DFFT_TAB
 
     // ---- phase 5: y = 4*lane + q; columns cbase + c (decode_main:185-188,
     // reconstructSub:138-149)
@@ -361,16 +272,7 @@
           ol[q] = vperm(rv.y, rv.x, 0x07050301u);
         }
       }
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const uint64_t col = cbase + c;
-        if (col >= ncols) break;
-        const uint32_t w0 = vperm(ol[0], oh[0], 0x0c0c0400u + 0x0101u * c) |
-                            (vperm(ol[1], oh[1], 0x0c0c0400u + 0x0101u * c) << 16);
-        const uint32_t w1 = vperm(ol[2], oh[2], 0x0c0c0400u + 0x0101u * c) |
-                            (vperm(ol[3], oh[3], 0x0c0c0400u + 0x0101u * c) << 16);
-        *reinterpret_cast<uint2 *>(O + (col * K + 4 * lane) * 2) = make_uint2(w0, w1);
-      }
+#include "dec_n1024_store.inc"
     }
     // the tile after next is published (wave 0 never idles: its columns start
     // the tile, so thread 0 and its wave get here); the atomic returned during

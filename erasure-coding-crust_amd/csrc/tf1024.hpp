@@ -1,6 +1,11 @@
 // tf1024.hpp — register-blocked 1024-point additive (I)FFT on one byte-planar
-// group per wave (4 codewords / pieces), shared by the k = 1024 encode and the
-// n = 4096 reconstruct (enc_k1024.hip, dec_n4096.hip).
+// group per wave (4 codewords / pieces).  Users: the k = 1024 encode
+// (enc_k1024.hip), the n = 4096 reconstruct (dec_n4096.hip), the n <= 1024
+// register-blocked reconstruct (dec_gen.hip) and, for the primitives (S16,
+// raddr, tlin, skew_idx, ib, bx, from_upper, swap_bit) and the radix-16
+// inverse pass ipass4 only, taken by name in dec_n1024_common.hpp, the
+// n = 1024, k = 256 reconstruct kernels (dec_n1024.hip, dec_n1024x.hip,
+// dec_n1024x_ragged.hip).
 //
 // A wave holds the 1024 positions of its group as 64 lanes x 16 registers
 // (uint2 {low bytes, high bytes} of 4 symbols each) in one of three layouts:
@@ -26,10 +31,18 @@ struct S16 {
   uint32_t l[16], h[16];
 };
 
+// region address of position v: 8-byte slots XOR-swizzled so that every
+// access pattern used below (positions varying in bits 4-8, 0-3+8, 0-4) is
+// bank-conflict free
 __host__ __device__ constexpr uint32_t raddr(uint32_t v) {
   const uint32_t f = (v & 31) ^ ((v >> 4) & 31);
   return ((v >> 5) << 8) | (f << 3);
 }
+// raddr is GF(2)-linear in v, so a wave's region access for position
+// (lane part) | (register part) is one v_xor of a per-lane LDS address with a
+// compile-time constant (lds_addr / lds_ld2 / lds_st2, ec_device.hpp).  The
+// region base (a multiple of 8 KB) has no bits in common with raddr (< 8 KB),
+// so it folds into the per-lane address too.
 
 // GF(2)-linear part of LdsTabs::addr: tlin(a | b) = tlin(a) ^ tlin(b) (disjoint a, b)
 __host__ __device__ constexpr uint32_t tlin(uint32_t idx) {
@@ -96,30 +109,70 @@ __device__ __forceinline__ void fb(S16 &s, int a, int b, const SubTab &T) {
   s.h[b] ^= s.h[a];
 }
 
+// IFFT stage 1 with F9 tables (the n = 1024, k = 256 kernels' image)
+__device__ __forceinline__ void ib(S16 &s, int a, int b, const F9Tab &T) {
+  s.l[b] ^= s.l[a];
+  s.h[b] ^= s.h[a];
+  mul_acc_f9(s.l[b], s.h[b], T, s.l[a], s.h[a]);
+}
+__device__ __forceinline__ void bx(S16 &s, int a, int b) {  // b ^= a
+  s.l[b] ^= s.l[a];
+  s.h[b] ^= s.h[a];
+}
+template <bool F9>
+struct Stage1Tab {
+  using type = Tab;
+};
+template <>
+struct Stage1Tab<true> {
+  using type = F9Tab;
+};
+
 // radix-16 passes over position bits B0..B0+3 held in registers; lb = tlin of
-// the lane part of the position.  The next block's table is requested one
-// step ahead of its use.
-template <int B0, int SM = kNoTower>
-__device__ __forceinline__ void ipass4(S16 &s, const uint8_t *tabs, uint32_t lb) {
-  Tab T[2];
-  SubTab U[2];
+// the lane part of the position: pos(r) = lane part | (r << B0).  15 tables
+// (8 + 4 + 2 + 1), each requested one step ahead of its use, so a table load
+// is always in flight behind the multiplies.
+//
+// The inverse pass is the one loop of every reconstruct and of the k = 1024
+// encode:
+//   tabs    where the tables are read from: a pointer to the image in LDS
+//           (tab_at above) or a tag type whose own tab_at overloads are found
+//           through it (n1024::Lds0: the image at LDS address 0);
+//   SM      the image's first subfield stage; F9: stage 1 takes F9 tables;
+//   NS, L   reconstruct_gen's n = 2^L < 1024: the pass runs the stages
+//           B0..B0+NS-1 of the local index pos & (n - 1).  When it holds the top
+//           local bit (B0 + NS == L) the lane part of a skew index has no bits
+//           above the stage, so a register block whose bits above the stage
+//           are 0 (blk < 2d) has skew skews[d - 1] = 0xFFFF at index 0:
+//           b ^= a only.  (A full pass of the 1024-point transform, NS = 4 and
+//           L = 10, never holds the top bit.)
+template <int B0, int SM = kNoTower, bool F9 = false, int NS = 4, int L = 10, class TP>
+__device__ __forceinline__ void ipass4(S16 &s, TP tabs, uint32_t lb) {
+  constexpr uint32_t NM = (1u << L) - 1;
+  constexpr bool TOP = B0 + NS == L;
+  Tab T[2];                            // general tables
+  typename Stage1Tab<F9>::type F[2];   // F9: stage 1
+  SubTab U[2];                         // stages >= SM: subfield tables
   const auto fetch = [&](int t, int blk, int slot) __attribute__((always_inline)) {
-    const uint32_t a = lb ^ tlin(skew_idx(uint32_t(blk) << B0, B0 + t));
+    const uint32_t a = lb ^ tlin(skew_idx((uint32_t(blk) << B0) & NM, B0 + t));
     if (B0 + t >= SM) tab_at(tabs, a, U[slot]);
+    else if (F9 && B0 + t == 1) tab_at(tabs, a, F[slot]);
     else tab_at(tabs, a, T[slot]);
   };
   fetch(0, 0, 0);
   int k = 0;
 #pragma unroll
-  for (int t = 0; t < 4; ++t) {
+  for (int t = 0; t < NS; ++t) {
     const int d = 1 << t;
 #pragma unroll
-    for (int blk = 0; blk < 16; blk += 2 * d, ++k) {
+    for (int blk = 0; blk < 16; blk += 2 * d, ++k) {  // one skew per block of 2d registers
       const int nt = blk + 2 * d < 16 ? t : t + 1, nblk = blk + 2 * d < 16 ? blk + 2 * d : 0;
-      if (nt < 4) fetch(nt, nblk, (k + 1) & 1);
+      if (nt < NS) fetch(nt, nblk, (k + 1) & 1);
 #pragma unroll
       for (int i = 0; i < d; ++i) {
-        if (B0 + t >= SM) ib(s, blk + i, blk + i + d, U[k & 1]);
+        if (TOP && ((blk << B0) & NM) >> (B0 + t + 1) == 0) bx(s, blk + i, blk + i + d);
+        else if (B0 + t >= SM) ib(s, blk + i, blk + i + d, U[k & 1]);
+        else if (F9 && B0 + t == 1) ib(s, blk + i, blk + i + d, F[k & 1]);
         else ib(s, blk + i, blk + i + d, T[k & 1]);
       }
     }
@@ -194,11 +247,6 @@ __device__ __forceinline__ void fpassC(S16 &s, const uint8_t *tabs) {
 // j = d has skew skews[d - 1] = 0xFFFF (no multiply, additive_fft.hpp:99-141):
 // stage 9 and stage 8's p9 = 0 block are b ^= a (IFFT) / b ^= a after an
 // a ^= 0 (FFT).
-__device__ __forceinline__ void bx(S16 &s, int a, int b) {  // b ^= a
-  s.l[b] ^= s.l[a];
-  s.h[b] ^= s.h[a];
-}
-
 template <int SM = kNoTower>
 __device__ __forceinline__ void ipassC0(S16 &s, const uint8_t *tabs) {
   TabAt<8, SM> Tb;
@@ -305,7 +353,9 @@ __device__ __forceinline__ void fft1024(S16 &s, const uint8_t *tabs, uint8_t *my
 }
 
 // ---- cross-lane helpers, layout bit maps, closed-form derivative and the
-// restricted FFT (reconstruct_gen, reconstruct_n4096)
+// restricted FFT (reconstruct_gen, reconstruct_n4096; from_upper and swap_bit
+// also serve the n = 1024, k = 256 kernels' own derivative and FFT,
+// dec_n1024_dfft.inc)
 __device__ __forceinline__ uint32_t dpp_up(uint32_t x, int b) {  // value of lane + 2^b (b < 4)
   switch (b) {
     case 0: return uint32_t(__builtin_amdgcn_update_dpp(0, int(x), 0x101, 0xf, 0xf, true));

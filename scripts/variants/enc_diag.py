@@ -61,7 +61,7 @@ os.makedirs(out, exist_ok=True)
 enc = flat("enc_k256w.hip")
 com = open(f"{CS}/enc_w_common.hpp").read()
 cim = open(f"{CS}/cimg.hpp").read()
-dec = open(f"{CS}/dec_n1024.hip").read()
+dec = flat("dec_n1024.hip")  # with dec_n1024_dfft.inc / dec_n1024_store.inc in place (dnoout)
 decx = flat("dec_n1024x.hip")
 
 

@@ -66,7 +66,7 @@ if kind == "enc":
     s = rep(s, "  }\n}\n\nbool k256_applicable", "  }\n" + FLUSH + "}\n\nbool k256_applicable")
     names = ["load", "barrier", "stores", "compute"]
 elif kind == "dec":
-    s = open(f"{ROOT}/erasure-coding-crust_amd/csrc/dec_n1024.hip").read()
+    s = flat("dec_n1024.hip")  # one source: the shared phases (dec_n1024_dfft.inc, dec_n1024_store.inc) in place
     s = rep(s, "namespace ecamd {\nnamespace {", "namespace ecamd {\n__device__ unsigned long long g_stamp[16];\nnamespace {")
     s = rep(s, "  Tabs::copy_image<THREADS>(tabs, t.timg_f9, tid0);  // F9 kind 0\n  __syncthreads();\n",
             "  Tabs::copy_image<THREADS>(tabs, t.timg_f9, tid0);  // F9 kind 0\n  __syncthreads();\n" + STAMP)
