@@ -48,16 +48,24 @@ def ref_encode(oracle, nv, plen):
 
 def pattern(oracle, nv, kind):
     """kind 0: a random threshold set; 1: every systematic row + parity up to the
-    threshold; 2: a random set of exactly k rows.  -> (present [n], locator mod 65535)"""
+    threshold; 2: a random set of exactly k rows; "P1" / "P2": the top and edge
+    patterns of tests/nv_boundaries.py (P1 sets the flags of rows >= nv too, which
+    stay erased: the locator is the one of the rows below nv).
+    -> (present [n], locator mod 65535)"""
     if (nv, kind) not in _PAT:
         n, k, thr = E.code_params(nv)
-        if kind == 1:
+        if kind in ("P1", "P2"):
+            import nv_boundaries
+            m = nv_boundaries.present(nv, kind)
+        elif kind == 1:
             m = np.zeros(n, np.uint8)
             m[:k] = 1
             m[k + synth.present_set(10**6 + nv + 1, nv - k, thr - k)] = 1
         else:
             m = synth.present_mask(10**6 + nv + kind, nv, thr if kind == 0 else k, n)
-        el = oracle.error_poly((m == 0).astype(np.uint8), n)[:n].astype(np.int64) % 65535
+        erased = m == 0
+        erased[nv:] = True
+        el = oracle.error_poly(erased.astype(np.uint8), n)[:n].astype(np.int64) % 65535
         m.setflags(write=False)
         _PAT[(nv, kind)] = (m, el)
     return _PAT[(nv, kind)]
