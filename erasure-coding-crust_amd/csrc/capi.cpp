@@ -158,7 +158,8 @@ bool reconstruct_host(const CodeParams &p, const std::vector<uint8_t> &present, 
       return false;
   } else if (all_systematic) {
     // every systematic shard is present: decode == interleave (exact)
-    if (!hip_check(launch_systematic(p, src, sl, dstride, 1, dst, out_bytes, c->stream, &sig),
+    // (one payload: no tile counter, systematic_w's static schedule)
+    if (!hip_check(launch_systematic(p, src, sl, dstride, 1, dst, out_bytes, nullptr, c->stream, &sig),
                    "systematic launch"))
       return false;
   } else {
@@ -341,18 +342,20 @@ NPRSResult ECCR_reconstruct_from_systematic(unsigned long nv, const ChunksList *
   const size_t used = sl / 2 * 2;
   HostCtx *c = host_ctx();
   DeviceState *d = c ? device_state() : nullptr;
-  const size_t in_bytes = size_t(p.k) * used, out_bytes = used * p.k;
+  // rows staged at a 16-B pitch, like every other staged layout (systematic_w's loads)
+  const size_t pitch = dev_pitch(used);
+  const size_t in_bytes = size_t(p.k) * pitch, out_bytes = used * p.k;
   if (!c || !d || !ensure_host(&c->h_in, &c->h_in_cap, in_bytes) ||
       !ensure_host(&c->h_out, &c->h_out_cap, out_bytes) ||
       !ensure_dev(reinterpret_cast<void **>(&c->d_in), &c->d_in_cap, in_bytes) ||
       !ensure_dev(reinterpret_cast<void **>(&c->d_out), &c->d_out_cap, out_bytes))
     return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
-  for (uint32_t y = 0; y < p.k; ++y) std::memcpy(c->h_in + y * used, slot[y]->data.array, used);
+  for (uint32_t y = 0; y < p.k; ++y) std::memcpy(c->h_in + y * pitch, slot[y]->data.array, used);
   CodeParams pk = p;
   pk.nv = p.k;  // staged layout holds only the k systematic shards
   if (!hip_check(hipMemcpyAsync(c->d_in, c->h_in, in_bytes, hipMemcpyHostToDevice, c->stream),
                  "H2D") ||
-      !hip_check(launch_systematic(pk, c->d_in, used, used, 1, c->d_out, out_bytes, c->stream),
+      !hip_check(launch_systematic(pk, c->d_in, used, pitch, 1, c->d_out, out_bytes, nullptr, c->stream),
                  "systematic launch") ||
       !hip_check(hipMemcpyAsync(c->h_out, c->d_out, out_bytes, hipMemcpyDeviceToHost, c->stream),
                  "D2H") ||
@@ -655,6 +658,66 @@ NPRSResult reconstruct_ragged(unsigned long nv, const uint8_t *d_shards, const E
     return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
   return result(NPRS_RESULT_OK);
 }
+
+// The scratch is systematic_w's tile counter only: a NULL or short workspace
+// runs the static schedule, as the encode's does (encode_batch).
+NPRSResult systematic_batch(unsigned long nv, const uint8_t *d_shards, unsigned long slen, unsigned long sstride,
+                            unsigned long batch, uint8_t *d_out, unsigned long ostride, hipStream_t s,
+                            const Workspace *ws) {
+  CodeParams p;
+  NPRSResult r = params_or_error(nv, &p);
+  if (r.tag != NPRS_RESULT_OK) return r;
+  if (sstride < slen || ostride < slen / 2 * 2 * p.k) return result(NPRS_RESULT_NON_UNIFORM_CHUNKS);
+  DeviceState *d = device_state();
+  if (!d) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
+  const bool counter = choose_systematic(p, slen / 2 * 2, sstride, batch, reinterpret_cast<uintptr_t>(d_shards),
+                                         reinterpret_cast<uintptr_t>(d_out), ostride, false) == Kernel::systematic_w;
+  const size_t need = counter ? systematic_scratch_bytes(p) : 0;
+  const bool skip = ws && (!ws->ptr || ws->bytes < need || reinterpret_cast<uintptr_t>(ws->ptr) % 256 != 0);
+  BatchScratch sc(d, skip ? 0 : need, s, ws);
+  if (!sc.ok) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
+  if (!hip_check(launch_systematic(p, d_shards, slen / 2 * 2, sstride, batch, d_out, ostride, sc.p, s),
+                 "systematic launch"))
+    return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
+  return result(NPRS_RESULT_OK);
+}
+
+NPRSResult systematic_ragged(unsigned long nv, const uint8_t *d_shards, const ECCR_AMD_RaggedItem *d_items,
+                             unsigned long batch, unsigned long max_slen, uint8_t *d_out, uint32_t *d_status,
+                             hipStream_t s, const Workspace *ws) {
+  CodeParams p;
+  NPRSResult r = params_or_error(nv, &p);
+  if (r.tag != NPRS_RESULT_OK) return r;
+  if (!d_shards || !d_items || !d_out) {
+    set_error("erasure_coding_crust(amd): systematic_ragged: a NULL buffer");
+    return result(NPRS_RESULT_BAD_PAYLOAD);
+  }
+  // tickets: column tiles x systematic_w's row blocks
+  const size_t tile = ragged_systematic_tile(p);
+  const size_t row_blocks = choose_systematic_ragged(p) == RaggedKernel::systematic_w_ragged
+                                ? systematic_w_row_blocks(p)
+                                : 1;
+  r = ragged_counts("systematic_ragged", batch, max_slen, (max_slen / 2 + tile - 1) / tile * row_blocks,
+                    NPRS_RESULT_NON_UNIFORM_CHUNKS);
+  if (r.tag != NPRS_RESULT_OK) return r;
+  if (!aligned16(d_shards) || !aligned16(d_out) || reinterpret_cast<uintptr_t>(d_items) % 8 != 0 ||
+      reinterpret_cast<uintptr_t>(d_status) % 4 != 0) {
+    set_error("erasure_coding_crust(amd): systematic_ragged: d_shards and d_out must be 16-B aligned, d_items 8-B");
+    return result(NPRS_RESULT_BAD_PAYLOAD);
+  }
+  const size_t need = ragged_systematic_workspace_bytes(p, batch);
+  if (ws && !ragged_workspace_ok(*ws, need)) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
+  DeviceState *d = device_state();
+  if (!d) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
+  BatchScratch sc(d, need, s, ws);
+  if (!sc.ok) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
+  if (!hip_check(launch_systematic_ragged(p, reinterpret_cast<const uint8_t *>(d_shards),
+                                          reinterpret_cast<const RaggedItem *>(d_items), batch, max_slen, d_out,
+                                          d_status, sc.p, s),
+                 "ragged systematic launch"))
+    return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
+  return result(NPRS_RESULT_OK);
+}
 }  // namespace
 
 extern "C" {
@@ -804,16 +867,62 @@ NPRSResult ECCR_AMD_locator_cache_stats(unsigned long *hits, unsigned long *miss
 NPRSResult ECCR_AMD_systematic_batch(unsigned long nv, const uint8_t *d_shards, unsigned long slen,
                                      unsigned long sstride, unsigned long batch, uint8_t *d_out,
                                      unsigned long ostride, void *stream) {
+  return systematic_batch(nv, d_shards, slen, sstride, batch, d_out, ostride, static_cast<hipStream_t>(stream),
+                          nullptr);
+}
+
+unsigned long ECCR_AMD_systematic_workspace_bytes(unsigned long nv, unsigned long slen, unsigned long batch) {
   CodeParams p;
-  NPRSResult r = params_or_error(nv, &p);
-  if (r.tag != NPRS_RESULT_OK) return r;
-  if (sstride < slen || ostride < slen / 2 * 2 * p.k) return result(NPRS_RESULT_NON_UNIFORM_CHUNKS);
-  if (!device_state()) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
-  if (!hip_check(launch_systematic(p, d_shards, slen / 2 * 2, sstride, batch, d_out, ostride,
-                                   static_cast<hipStream_t>(stream)),
-                 "systematic launch"))
-    return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
-  return result(NPRS_RESULT_OK);
+  if (code_params(nv, &p) != ParamError::kOk || slen < 2 || batch == 0) return 0;
+  return systematic_scratch_bytes(p);
+}
+
+NPRSResult ECCR_AMD_systematic_batch_ws(unsigned long nv, const uint8_t *d_shards, unsigned long slen,
+                                        unsigned long sstride, unsigned long batch, uint8_t *d_out,
+                                        unsigned long ostride, void *d_workspace, unsigned long workspace_bytes,
+                                        void *stream) {
+  const Workspace ws{d_workspace, workspace_bytes};
+  return systematic_batch(nv, d_shards, slen, sstride, batch, d_out, ostride, static_cast<hipStream_t>(stream),
+                          &ws);
+}
+
+const char *ECCR_AMD_systematic_kernel(unsigned long nv, const uint8_t *d_shards, unsigned long slen,
+                                       unsigned long sstride, unsigned long batch, const uint8_t *d_out,
+                                       unsigned long ostride) {
+  CodeParams p;
+  if (code_params(nv, &p) != ParamError::kOk) return nullptr;
+  if (sstride < slen || ostride < slen / 2 * 2 * p.k) return nullptr;
+  return kernel_name(choose_systematic(p, slen / 2 * 2, sstride, batch, reinterpret_cast<uintptr_t>(d_shards),
+                                       reinterpret_cast<uintptr_t>(d_out), ostride, false));
+}
+
+NPRSResult ECCR_AMD_systematic_ragged(unsigned long nv, const uint8_t *d_shards, const ECCR_AMD_RaggedItem *d_items,
+                                      unsigned long batch, unsigned long max_slen, uint8_t *d_out,
+                                      uint32_t *d_status, void *stream) {
+  return systematic_ragged(nv, d_shards, d_items, batch, max_slen, d_out, d_status, static_cast<hipStream_t>(stream),
+                           nullptr);
+}
+
+NPRSResult ECCR_AMD_systematic_ragged_ws(unsigned long nv, const uint8_t *d_shards,
+                                         const ECCR_AMD_RaggedItem *d_items, unsigned long batch,
+                                         unsigned long max_slen, uint8_t *d_out, uint32_t *d_status,
+                                         void *d_workspace, unsigned long workspace_bytes, void *stream) {
+  const Workspace ws{d_workspace, workspace_bytes};
+  return systematic_ragged(nv, d_shards, d_items, batch, max_slen, d_out, d_status, static_cast<hipStream_t>(stream),
+                           &ws);
+}
+
+unsigned long ECCR_AMD_systematic_ragged_workspace_bytes(unsigned long nv, unsigned long batch,
+                                                         unsigned long max_slen) {
+  CodeParams p;
+  if (code_params(nv, &p) != ParamError::kOk || batch == 0 || batch >= (1ul << 31) || max_slen == 0) return 0;
+  return ragged_systematic_workspace_bytes(p, batch);
+}
+
+const char *ECCR_AMD_systematic_ragged_kernel(unsigned long nv) {
+  CodeParams p;
+  if (code_params(nv, &p) != ParamError::kOk) return nullptr;
+  return ragged_kernel_name(choose_systematic_ragged(p));
 }
 
 NPRSResult ECCR_AMD_encode_ragged(unsigned long nv, const uint8_t *d_payloads,

@@ -468,6 +468,29 @@ __global__ void __launch_bounds__(kBlock) systematic_g(const uint8_t *__restrict
   signal_end(sig_flag, sig_v);  // (single-workgroup launches only)
 }
 
+// the ragged form (k < 16): blockIdx.y over the items, an item without tiles in
+// the plan's prefix (one that broke the contract) skipped whole
+__global__ void __launch_bounds__(kBlock) systematic_g_ragged(const uint8_t *__restrict__ shards,
+                                                              const RaggedItem *__restrict__ items,
+                                                              const uint32_t *__restrict__ tile_first, int logk,
+                                                              uint8_t *__restrict__ out, uint32_t batch) {
+  const int k = 1 << logk;
+  for (uint32_t b = blockIdx.y; b < batch; b += gridDim.y) {
+    if (tile_first[b + 1] == tile_first[b]) continue;
+    const RaggedItem it = items[b];
+    const uint8_t *SH = shards + it.shard_off;
+    uint8_t *O = out + it.payload_off;
+    const uint64_t total = it.shard_len / 2 * k;
+    for (uint64_t e = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; e < total;
+         e += uint64_t(gridDim.x) * blockDim.x) {
+      const uint64_t i = e >> logk;
+      const int y = int(e & (k - 1));
+      O[2 * e] = SH[uint64_t(y) * it.shard_stride + 2 * i];
+      O[2 * e + 1] = SH[uint64_t(y) * it.shard_stride + 2 * i + 1];
+    }
+  }
+}
+
 // completion signal of a per-call C-ABI call: after the call's work on the
 // stream, one lane stores `v` to a pinned host word at system scope; the host
 // spins on it (a host spin on a kernel-written flag is ~5 us faster per round
@@ -534,6 +557,7 @@ const char *kernel_name(Kernel k) {
     ECAMD_NAME(encode_k512w) ECAMD_NAME(encode_k1024) ECAMD_NAME(encode_g)
     ECAMD_NAME(reconstruct_n1024x) ECAMD_NAME(reconstruct_n1024) ECAMD_NAME(reconstruct_n1024_packed)
     ECAMD_NAME(reconstruct_n4096) ECAMD_NAME(reconstruct_gen) ECAMD_NAME(reconstruct_g)
+    ECAMD_NAME(systematic_w) ECAMD_NAME(systematic_g)
 #undef ECAMD_NAME
     case Kernel::invalid: break;
   }
@@ -762,10 +786,32 @@ hipError_t launch_reconstruct(const CodeParams &p, const DevTables &t, const uin
   return hipGetLastError();
 }
 
+// systematic_w reads rows with 16-B loads and writes the output with 16-B
+// stores (a single payload's out pitch is never applied); k < 16 has output
+// runs under 32 B per column, which stay with the element-wise kernel.  A
+// per-call launch small enough for ONE systematic_g workgroup keeps it: that
+// workgroup stores the completion signal itself (HostSig), which a separate
+// signal kernel after systematic_w would not match in latency.
+Kernel choose_systematic(const CodeParams &p, size_t slen, size_t sstride, size_t batch, uintptr_t shards,
+                         uintptr_t out, size_t ostride, bool host_signal) {
+  if (batch == 0 || slen < 2) return Kernel::invalid;
+  if (host_signal && batch == 1 && slen / 2 * p.k <= size_t(kBlock)) return Kernel::systematic_g;
+  const bool aligned = shards % 16 == 0 && sstride % 16 == 0 && out % 16 == 0 && (batch == 1 || ostride % 16 == 0);
+  return p.k >= 16 && aligned ? Kernel::systematic_w : Kernel::systematic_g;
+}
+
+size_t systematic_scratch_bytes(const CodeParams &p) { return p.k >= 16 ? 256 : 0; }
+
 hipError_t launch_systematic(const CodeParams &p, const uint8_t *d_shards, size_t slen,
                              size_t sstride, size_t batch, uint8_t *d_out, size_t ostride,
-                             hipStream_t s, HostSig *sig) {
-  if (batch == 0 || slen < 2) return hipSuccess;
+                             void *scratch, hipStream_t s, HostSig *sig) {
+  switch (choose_systematic(p, slen, sstride, batch, reinterpret_cast<uintptr_t>(d_shards),
+                            reinterpret_cast<uintptr_t>(d_out), ostride, sig && sig->flag)) {
+    case Kernel::systematic_w:
+      return launch_systematic_w(p, d_shards, slen, sstride, batch, d_out, ostride, scratch, s);
+    case Kernel::systematic_g: break;
+    default: return hipSuccess;  // an empty call
+  }
   const size_t total = slen / 2 * p.k;
   size_t blocks = (total + kBlock - 1) / kBlock;
   if (blocks > 4096) blocks = 4096;
@@ -800,6 +846,23 @@ size_t ragged_reconstruct_g_scratch_bytes(const CodeParams &p, size_t batch, siz
   if (p.n <= uint32_t(kLdsSlots)) return 0;
   const size_t tiles = (max_slen / 2 + 3) / 4;
   return tiles * grid_y(batch) * 2 * size_t(p.n) * sizeof(uint2);
+}
+
+// columns per plan tile of the systematic ragged kernels: systematic_w's
+// tile; below k = 16 (systematic_g_ragged only asks whether an item has tiles)
+// the 4096 columns of one sweep of its grid
+uint32_t ragged_systematic_tile(const CodeParams &p) {
+  return choose_systematic_ragged(p) == RaggedKernel::systematic_w_ragged ? systematic_w_cols(p) : 4096u;
+}
+
+hipError_t launch_systematic_g_ragged(const CodeParams &p, const uint8_t *d_shards, const RaggedItem *d_items,
+                                      size_t batch, size_t max_slen, uint8_t *d_out, void *ws, hipStream_t s) {
+  const size_t total = max_slen / 2 * p.k;
+  size_t blocks = (total + kBlock - 1) / kBlock;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(systematic_g_ragged, dim3(unsigned(blocks), unsigned(grid_y(batch))), dim3(kBlock), 0, s,
+                     d_shards, d_items, ragged_first(ws), ilog2(p.k), d_out, uint32_t(batch));
+  return hipGetLastError();
 }
 
 hipError_t launch_encode_g_ragged(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,

@@ -105,8 +105,8 @@ size_t reconstruct_scratch_bytes(const CodeParams &p, size_t shard_len, size_t b
 
 // The kernel a batch call runs: decided by the code, the lengths, the batch
 // and the alignment of every base and pitch, in choose_encode /
-// choose_reconstruct and nowhere else (launch_encode / launch_reconstruct
-// switch on the result).  `invalid`: nothing is launched (an empty call, or a
+// choose_reconstruct / choose_systematic and nowhere else (launch_encode /
+// launch_reconstruct / launch_systematic switch on the result).  `invalid`: nothing is launched (an empty call, or a
 // packed form whose flattened space passes 2^32: hipErrorInvalidValue).
 enum class Kernel {
   invalid,
@@ -122,6 +122,8 @@ enum class Kernel {
   reconstruct_n4096,
   reconstruct_gen,
   reconstruct_g,
+  systematic_w,
+  systematic_g,
 };
 const char *kernel_name(Kernel k);  // the enumerator's name; nullptr for invalid
 
@@ -176,9 +178,26 @@ hipError_t launch_reconstruct(const CodeParams &p, const DevTables &t, const uin
                               const uint16_t *d_err_log, const uint32_t *d_pattern, size_t batch,
                               uint8_t *d_out, size_t out_stride, void *scratch, hipStream_t s);
 
+// The systematic recovery's kernel (a pure host function, like the two above):
+// systematic_w (sys_w.hip) for k >= 16 with the shard base and pitch, the out
+// base and (batch > 1) the out pitch on 16 B; systematic_g otherwise, and for
+// a per-call launch whose single workgroup stores the completion signal itself
+// (host_signal: the caller passes a HostSig).
+Kernel choose_systematic(const CodeParams &p, size_t shard_len, size_t shard_stride, size_t batch,
+                         uintptr_t shards, uintptr_t out, size_t out_stride, bool host_signal);
+// scratch (nullable: static tile schedule): systematic_w's tile counter,
+// systematic_scratch_bytes
+size_t systematic_scratch_bytes(const CodeParams &p);
 hipError_t launch_systematic(const CodeParams &p, const uint8_t *d_shards, size_t shard_len,
                              size_t shard_stride, size_t batch, uint8_t *d_out, size_t out_stride,
-                             hipStream_t s, HostSig *sig = nullptr);
+                             void *scratch, hipStream_t s, HostSig *sig = nullptr);
+// systematic_w's tile: columns per tile (16384 / min(k, 256)) and the row
+// blocks a column tile is walked in (k / 256 above k = 256)
+uint32_t systematic_w_cols(const CodeParams &p);
+uint32_t systematic_w_row_blocks(const CodeParams &p);
+hipError_t launch_systematic_w(const CodeParams &p, const uint8_t *d_shards, size_t shard_len,
+                               size_t shard_stride, size_t batch, uint8_t *d_out, size_t out_stride,
+                               void *scratch, hipStream_t s);
 
 // the per-call encode of tiny codes (enc_tiny.hip): n <= kTinyMaxN, payload
 // <= kTinyBytes and the code's tables carried in the kernel arguments, one workgroup, output rows

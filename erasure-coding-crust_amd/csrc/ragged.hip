@@ -105,6 +105,8 @@ const char *ragged_kernel_name(RaggedKernel k) {
     case RaggedKernel::encode_g_ragged: return "encode_g_ragged";
     case RaggedKernel::reconstruct_n1024x_ragged: return "reconstruct_n1024x_ragged";
     case RaggedKernel::reconstruct_g_ragged: return "reconstruct_g_ragged";
+    case RaggedKernel::systematic_w_ragged: return "systematic_w_ragged";
+    case RaggedKernel::systematic_g_ragged: return "systematic_g_ragged";
   }
   return nullptr;
 }
@@ -117,6 +119,13 @@ RaggedKernel choose_encode_ragged(const CodeParams &p) {
 RaggedKernel choose_reconstruct_ragged(const CodeParams &p) {
   return n1024_applicable(p) ? RaggedKernel::reconstruct_n1024x_ragged : RaggedKernel::reconstruct_g_ragged;
 }
+
+// (the contract puts every item's offsets and pitch on 16 B: k alone decides)
+RaggedKernel choose_systematic_ragged(const CodeParams &p) {
+  return p.k >= 16 ? RaggedKernel::systematic_w_ragged : RaggedKernel::systematic_g_ragged;
+}
+
+size_t ragged_systematic_workspace_bytes(const CodeParams &, size_t batch) { return ragged_scratch_offset(batch); }
 
 size_t ragged_encode_workspace_bytes(const CodeParams &p, size_t batch, size_t max_plen) {
   const size_t own = choose_encode_ragged(p) == RaggedKernel::encode_g_ragged
@@ -157,6 +166,18 @@ hipError_t launch_reconstruct_ragged(const CodeParams &p, const DevTables &t, co
              ? launch_reconstruct_n1024x_ragged(p, t, d_present, d_err_log, d_pattern, batch, max_slen, ws, s)
              : launch_reconstruct_g_ragged(p, t, d_shards, d_items, d_present, d_err_log, d_pattern, batch,
                                            max_slen, d_out, ws, s);
+}
+
+hipError_t launch_systematic_ragged(const CodeParams &p, const uint8_t *d_shards, const RaggedItem *d_items,
+                                    size_t batch, size_t max_slen, uint8_t *d_out, uint32_t *d_status, void *ws,
+                                    hipStream_t s) {
+  if (const hipError_t e = launch_ragged_plan(p, d_items, batch, max_slen, true, ragged_systematic_tile(p), d_shards,
+                                              d_out, ws, d_status, s);
+      e != hipSuccess)
+    return e;
+  return choose_systematic_ragged(p) == RaggedKernel::systematic_w_ragged
+             ? launch_systematic_w_ragged(p, batch, max_slen, ws, s)
+             : launch_systematic_g_ragged(p, d_shards, d_items, batch, max_slen, d_out, ws, s);
 }
 
 }  // namespace ecamd

@@ -80,15 +80,25 @@ inline uint32_t *ragged_first(void *ws) {
 
 // The kernels of a ragged call (choose_*_ragged: by n_validators alone, the
 // contract makes every item's alignment the same)
-enum class RaggedKernel { encode_k256w_ragged, encode_g_ragged, reconstruct_n1024x_ragged, reconstruct_g_ragged };
+enum class RaggedKernel {
+  encode_k256w_ragged,
+  encode_g_ragged,
+  reconstruct_n1024x_ragged,
+  reconstruct_g_ragged,
+  systematic_w_ragged,
+  systematic_g_ragged,
+};
 const char *ragged_kernel_name(RaggedKernel k);
 RaggedKernel choose_encode_ragged(const CodeParams &p);
 RaggedKernel choose_reconstruct_ragged(const CodeParams &p);
+RaggedKernel choose_systematic_ragged(const CodeParams &p);  // systematic_w_ragged from k = 16 on
 uint32_t ragged_encode_tile(const CodeParams &p);       // pieces per tile of that kernel
 uint32_t ragged_reconstruct_tile(const CodeParams &p);  // columns per tile
+uint32_t ragged_systematic_tile(const CodeParams &p);   // columns per (column) tile
 
 size_t ragged_encode_workspace_bytes(const CodeParams &p, size_t batch, size_t max_plen);
 size_t ragged_reconstruct_workspace_bytes(const CodeParams &p, size_t batch, size_t max_slen);
+size_t ragged_systematic_workspace_bytes(const CodeParams &p, size_t batch);  // the plan alone
 
 // host copy of the items -> status {items that break the contract, lowest such index}
 void ragged_check_host(const CodeParams &p, const RaggedItem *items, size_t batch, uint64_t max_len,
@@ -110,6 +120,11 @@ hipError_t launch_reconstruct_ragged(const CodeParams &p, const DevTables &t, co
                                      const uint16_t *d_err_log, const uint32_t *d_pattern, size_t batch,
                                      size_t max_slen, uint8_t *d_out, uint32_t *d_status, void *ws,
                                      hipStream_t s);
+// the systematic recovery of every item from its rows y < k (items in the
+// reconstruct's meaning: payload_off in d_out)
+hipError_t launch_systematic_ragged(const CodeParams &p, const uint8_t *d_shards, const RaggedItem *d_items,
+                                    size_t batch, size_t max_slen, uint8_t *d_out, uint32_t *d_status, void *ws,
+                                    hipStream_t s);
 // the kernels' own launchers (enc_k256w_ragged.hip, dec_n1024x_ragged.hip,
 // ec_kernels.hip), after the plan on the same stream; the persistent kernels
 // take the buffers and the items from the plan's header
@@ -125,6 +140,9 @@ hipError_t launch_reconstruct_g_ragged(const CodeParams &p, const DevTables &t, 
                                        const RaggedItem *d_items, const uint8_t *d_present,
                                        const uint16_t *d_err_log, const uint32_t *d_pattern, size_t batch,
                                        size_t max_slen, uint8_t *d_out, void *ws, hipStream_t s);
+hipError_t launch_systematic_w_ragged(const CodeParams &p, size_t batch, size_t max_slen, void *ws, hipStream_t s);
+hipError_t launch_systematic_g_ragged(const CodeParams &p, const uint8_t *d_shards, const RaggedItem *d_items,
+                                      size_t batch, size_t max_slen, uint8_t *d_out, void *ws, hipStream_t s);
 size_t ragged_encode_g_scratch_bytes(const CodeParams &p, size_t batch, size_t max_plen);
 size_t ragged_reconstruct_g_scratch_bytes(const CodeParams &p, size_t batch, size_t max_slen);
 

@@ -117,6 +117,13 @@ def lib():
             "ECCR_AMD_error_locator": (NPRSResult, [ul, vp, ul, vp, vp]),
             "ECCR_AMD_reconstruct_batch": (NPRSResult, [ul, vp, ul, ul, vp, vp, ul, vp, ul, vp]),
             "ECCR_AMD_systematic_batch": (NPRSResult, [ul, vp, ul, ul, ul, vp, ul, vp]),
+            "ECCR_AMD_systematic_batch_ws": (NPRSResult, [ul, vp, ul, ul, ul, vp, ul, vp, ul, vp]),
+            "ECCR_AMD_systematic_workspace_bytes": (ul, [ul, ul, ul]),
+            "ECCR_AMD_systematic_kernel": (C.c_char_p, [ul, vp, ul, ul, ul, vp, ul]),
+            "ECCR_AMD_systematic_ragged": (NPRSResult, [ul, vp, vp, ul, ul, vp, vp, vp]),
+            "ECCR_AMD_systematic_ragged_ws": (NPRSResult, [ul, vp, vp, ul, ul, vp, vp, vp, ul, vp]),
+            "ECCR_AMD_systematic_ragged_workspace_bytes": (ul, [ul, ul, ul]),
+            "ECCR_AMD_systematic_ragged_kernel": (C.c_char_p, [ul]),
             "ECCR_AMD_dedup_patterns": (NPRSResult, [ul, vp, ul, vp, vp]),
             "ECCR_AMD_error_locator_patterns": (NPRSResult, [ul, vp, vp, ul, vp, vp]),
             "ECCR_AMD_reconstruct_batch_patterns": (NPRSResult, [ul, vp, ul, ul, vp, vp, vp, ul, vp,
@@ -410,6 +417,27 @@ def systematic_batch(nv, d_shards, shard_len_, shard_stride, batch, d_out, out_s
            "systematic_batch")
 
 
+def systematic_workspace_bytes(nv, shard_len_, batch):
+    """Device scratch bytes of systematic_batch_ws (the tile counter of systematic_w)."""
+    return int(lib().ECCR_AMD_systematic_workspace_bytes(nv, shard_len_, batch))
+
+
+def systematic_batch_ws(nv, d_shards, shard_len_, shard_stride, batch, d_out, out_stride, ws,
+                        stream=None):
+    """systematic_batch on caller-owned scratch `ws` (None: the static tile schedule)."""
+    wp, wb = _ws(ws)
+    _check(lib().ECCR_AMD_systematic_batch_ws(nv, _p(d_shards), shard_len_, shard_stride, batch,
+                                              _p(d_out), out_stride, wp, wb, _stream(stream)),
+           "systematic_batch_ws")
+
+
+def systematic_kernel(nv, d_shards, shard_len_, shard_stride, batch, d_out, out_stride):
+    """Name of the kernel systematic_batch would launch for these arguments, or None."""
+    r = lib().ECCR_AMD_systematic_kernel(nv, _p(d_shards), shard_len_, shard_stride, batch,
+                                         _p(d_out), out_stride)
+    return None if r is None else r.decode()
+
+
 # ------------------------------------------------- ragged batches (ec_amd.h)
 
 
@@ -499,6 +527,29 @@ def reconstruct_ragged(nv, d_shards, d_items, d_present, d_err_log, batch, max_s
                                                 _p(d_err_log), _opt(d_pattern), batch, max_shard_len,
                                                 _p(d_out), _opt(d_status), wp, wb, _stream(stream)),
            "reconstruct_ragged_ws")
+
+
+def systematic_ragged(nv, d_shards, d_items, batch, max_shard_len, d_out, d_status=None, ws=None,
+                      stream=None):
+    """ECCR_AMD_systematic_ragged, or its _ws form when a workspace tensor is given."""
+    if ws is None:
+        _check(lib().ECCR_AMD_systematic_ragged(nv, _p(d_shards), _p(d_items), batch, max_shard_len,
+                                                _p(d_out), _opt(d_status), _stream(stream)),
+               "systematic_ragged")
+        return
+    wp, wb = _ws(ws)
+    _check(lib().ECCR_AMD_systematic_ragged_ws(nv, _p(d_shards), _p(d_items), batch, max_shard_len,
+                                               _p(d_out), _opt(d_status), wp, wb, _stream(stream)),
+           "systematic_ragged_ws")
+
+
+def systematic_ragged_workspace_bytes(nv, batch, max_shard_len):
+    return int(lib().ECCR_AMD_systematic_ragged_workspace_bytes(nv, batch, max_shard_len))
+
+
+def systematic_ragged_kernel(nv):
+    r = lib().ECCR_AMD_systematic_ragged_kernel(nv)
+    return None if r is None else r.decode()
 
 
 def encode_ragged_kernel(nv):

@@ -311,11 +311,63 @@ int ECCR_AMD_reconstruct_n1024x_waves(unsigned long shard_len);
 struct NPRSResult ECCR_AMD_locator_cache_stats(unsigned long *hits, unsigned long *misses);
 
 /* Device-resident batch reconstruct_from_systematic (shards 0..k-1 of each
- * payload, same [batch][n_validators][shard_stride] layout). */
+ * payload, same [batch][n_validators][shard_stride] layout): writes
+ * shard_len / 2 * 2 * k bytes per payload at d_out + b * out_stride and never
+ * a byte outside them.  Rows y >= k are not read.  With k >= 16 and d_shards,
+ * shard_stride, d_out and (batch > 1) out_stride on 16 B the call runs the
+ * tiled transpose systematic_w, otherwise the element-wise systematic_g
+ * (ECCR_AMD_systematic_kernel names the choice); the bytes are the same.
+ *
+ * Workspace: systematic_w hands out its tiles from a counter.  The plain call
+ * keeps it in the scratch private to (device, stream); the _ws form takes the
+ * caller's (256-B aligned, ECCR_AMD_systematic_workspace_bytes), allocates
+ * nothing and can be captured into a hipGraph.  A NULL, short or misaligned
+ * workspace is not an error: the kernel then runs a static tile schedule, as
+ * the encode does.  ECCR_AMD_systematic_workspace_bytes is 0 for an invalid
+ * n_validators, shard_len < 2 or batch == 0. */
 struct NPRSResult ECCR_AMD_systematic_batch(unsigned long n_validators, const uint8_t *d_shards,
                                             unsigned long shard_len, unsigned long shard_stride,
                                             unsigned long batch, uint8_t *d_out,
                                             unsigned long out_stride, void *stream);
+unsigned long ECCR_AMD_systematic_workspace_bytes(unsigned long n_validators, unsigned long shard_len,
+                                                  unsigned long batch);
+struct NPRSResult ECCR_AMD_systematic_batch_ws(unsigned long n_validators, const uint8_t *d_shards,
+                                               unsigned long shard_len, unsigned long shard_stride,
+                                               unsigned long batch, uint8_t *d_out,
+                                               unsigned long out_stride, void *d_workspace,
+                                               unsigned long workspace_bytes, void *stream);
+/* The kernel ECCR_AMD_systematic_batch (and _ws) would launch for exactly
+ * these arguments: systematic_w or systematic_g, NULL where nothing would be
+ * launched (invalid parameters, shard_len < 2, an empty batch).  Host-only, as
+ * ECCR_AMD_encode_kernel. */
+const char *ECCR_AMD_systematic_kernel(unsigned long n_validators, const uint8_t *d_shards,
+                                       unsigned long shard_len, unsigned long shard_stride,
+                                       unsigned long batch, const uint8_t *d_out,
+                                       unsigned long out_stride);
+
+/* The ragged form (see "ragged batches" above): item b's rows y < k at
+ * d_shards + shard_off (pitch shard_stride) -> shard_len * k bytes at d_out +
+ * payload_off.  The items have the reconstruct's meaning, and so have the
+ * contract, the host validation and its tags (NON_UNIFORM_CHUNKS for a maximum
+ * of 0, UNKNOWN_RECONSTRUCTION for a bad _ws workspace), d_status and the
+ * graph-capture rules; ECCR_AMD_ragged_check(reconstruct = 1) is the item test.
+ * An item that breaks the contract is skipped whole.  The work-queue bound of
+ * the host validation counts systematic_w's tiles: 16384 / min(k, 256) columns
+ * by k / 256 row blocks above k = 256.  k >= 16 runs systematic_w_ragged,
+ * smaller k systematic_g_ragged (ECCR_AMD_systematic_ragged_kernel, by
+ * n_validators alone; NULL for an invalid n_validators). */
+struct NPRSResult ECCR_AMD_systematic_ragged(unsigned long n_validators, const uint8_t *d_shards,
+                                             const ECCR_AMD_RaggedItem *d_items, unsigned long batch,
+                                             unsigned long max_shard_len, uint8_t *d_out,
+                                             uint32_t *d_status, void *stream);
+struct NPRSResult ECCR_AMD_systematic_ragged_ws(unsigned long n_validators, const uint8_t *d_shards,
+                                                const ECCR_AMD_RaggedItem *d_items, unsigned long batch,
+                                                unsigned long max_shard_len, uint8_t *d_out,
+                                                uint32_t *d_status, void *d_workspace,
+                                                unsigned long workspace_bytes, void *stream);
+unsigned long ECCR_AMD_systematic_ragged_workspace_bytes(unsigned long n_validators, unsigned long batch,
+                                                         unsigned long max_shard_len);
+const char *ECCR_AMD_systematic_ragged_kernel(unsigned long n_validators);
 
 /* ---- host-resident batches --------------------------
  * Stream a host batch through the device in chunks of `chunk` payloads (0 =
