@@ -1339,7 +1339,9 @@ def test_systematic_tiny_boundaries(oracle, nv):
 def test_encode_ws_without_counter(oracle):
     """a workspace below the queried size (here NULL / 0 bytes, as a
     caller that cached an older size would pass) runs the k = 256 / 512 / 1024
-    encodes on their static tile schedule instead of failing; bit-exact."""
+    encodes on their static tile schedule instead of failing; bit-exact.  These
+    shapes have fewer tiles than workgroups: the static stride past a workgroup's
+    first tile (cur + gridDim.x) is covered by tests/test_tile_loops.py."""
     import torch
     for nv, plen, B in ((1024, 70_000, 5), (600, 50_000, 3), (2500, 60_000, 3), (4096, 80_000, 3),
                          (300, 40_000, 2), (100, 40_000, 2)):
