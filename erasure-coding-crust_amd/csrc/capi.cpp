@@ -32,13 +32,6 @@ struct Workspace {  // caller-owned device scratch (the *_ws batch entry points)
   size_t bytes;
 };
 
-NPRSResult result(NPRSResult_Tag tag) {
-  NPRSResult r;
-  std::memset(&r, 0, sizeof r);
-  r.tag = tag;
-  return r;
-}
-
 [[noreturn]] void contract_violation(const char *what) {  // Rust assert! == abort
   std::fprintf(stderr, "erasure_coding_crust(amd): contract violation: %s\n", what);
   std::abort();
@@ -52,17 +45,6 @@ NPRSResult params_or_error(unsigned long nv, CodeParams *p) {
     default: return result(NPRS_RESULT_OK);
   }
 }
-
-bool hip_check(hipError_t e, const char *what) {
-  if (e == hipSuccess) return true;
-  set_error(std::string("erasure_coding_crust(amd): ") + what + ": " + hipGetErrorString(e));
-  return false;
-}
-
-// device row pitch of the per-call paths: 16-B aligned rows for the fast
-// kernels; the host staging buffers use the same pitch, so every host<->device
-// copy is one linear transfer (a 2-D copy of narrow rows costs ~10 us per row)
-inline size_t dev_pitch(size_t sl) { return (sl + 15) / 16 * 16; }
 
 // Calls whose input and output together stay below this run the kernel on
 // the pinned staging buffers themselves (device-mapped host memory, read and
@@ -99,9 +81,8 @@ bool encode_host(const CodeParams &p, const uint8_t *payload, size_t len, HostCt
     if (!lease.ok()) return false;
     std::memcpy(c->h_in, payload, len);
     HostSig sig = call_signal(c);  // stored by the encode kernel itself when it can (HostSig)
-    if (!hip_check(launch_encode(p, device_tables(d), c->h_in, len, len, 1, c->h_out, dstride,
-                                 lease.ptr(), c->stream, &sig),
-                   "encode launch") ||
+    const EncodeCall call{c->h_in, len, len, 1, c->h_out, dstride};
+    if (!hip_check(launch_encode(p, device_tables(d), call, lease.ptr(), c->stream, &sig), "encode launch") ||
         !finish_call(c, "encode", &sig))
       return false;
     *sl_out = sl;
@@ -114,12 +95,10 @@ bool encode_host(const CodeParams &p, const uint8_t *payload, size_t len, HostCt
     return false;
   ScratchLease lease(d, encode_scratch_bytes(p, len, 1), c->stream);
   if (!lease.ok()) return false;
-  void *scratch = lease.ptr();
   std::memcpy(c->h_in, payload, len);
+  const EncodeCall call{c->d_in, len, len, 1, c->d_out, dstride};
   if (!hip_check(hipMemcpyAsync(c->d_in, c->h_in, len, hipMemcpyHostToDevice, c->stream), "H2D") ||
-      !hip_check(launch_encode(p, device_tables(d), c->d_in, len, len, 1, c->d_out, dstride,
-                               scratch, c->stream),
-                 "encode launch") ||
+      !hip_check(launch_encode(p, device_tables(d), call, lease.ptr(), c->stream), "encode launch") ||
       !hip_check(hipMemcpyAsync(c->h_out, c->d_out, out_bytes, hipMemcpyDeviceToHost, c->stream),
                  "D2H") ||
       !hip_check(hipStreamSynchronize(c->stream), "encode"))
@@ -133,15 +112,13 @@ bool reconstruct_host(const CodeParams &p, const std::vector<uint8_t> &present, 
                       HostCtx *c) {
   DeviceState *d = device_state();
   if (!d) return false;
-  const size_t in_bytes = size_t(p.nv) * sl, out_bytes = sl * p.k;
-  const size_t dstride = dev_pitch(sl);
+  const size_t out_bytes = sl * p.k, dstride = dev_pitch(sl);
   if (!ensure_dev(reinterpret_cast<void **>(&c->d_in), &c->d_in_cap, size_t(p.nv) * dstride) ||
       !ensure_dev(reinterpret_cast<void **>(&c->d_out), &c->d_out_cap, out_bytes) ||
       !ensure_host(&c->h_out, &c->h_out_cap, out_bytes))
     return false;
   bool all_systematic = true;
   for (uint32_t y = 0; y < p.k; ++y) all_systematic &= present[y] != 0;
-  (void)in_bytes;
   // small calls: the kernels read the staged shards and write the payload
   // in pinned host memory (kDirectBytes)
   const bool direct = size_t(p.nv) * dstride + out_bytes <= kDirectBytes;
@@ -152,54 +129,45 @@ bool reconstruct_host(const CodeParams &p, const std::vector<uint8_t> &present, 
                             "H2D"))
     return false;
   HostSig sig = direct ? call_signal(c) : HostSig();
-  if (all_systematic && direct && systematic_tiny_applicable(p, sl)) {
+  // the tail of every branch: the payload copied back unless direct, then the
+  // wait.  Kernels only (direct): the signal-kernel wait; after a D2H copy the
+  // copy-to-kernel hand-off makes that slower than waiting on the stream
+  // 
+  const auto finish = [&](bool launched) {
+    return launched &&
+           (direct ||
+            hip_check(hipMemcpyAsync(c->h_out, c->d_out, out_bytes, hipMemcpyDeviceToHost, c->stream), "D2H")) &&
+           (direct ? finish_call(c, "reconstruct", &sig) : hip_check(hipStreamSynchronize(c->stream), "reconstruct"));
+  };
+  if (all_systematic && direct && systematic_tiny_applicable(p, sl))
     // tiny calls: the k systematic shards ride in the kernel arguments (enc_tiny.hip)
-    if (!hip_check(launch_systematic_tiny(p, c->h_in, sl, dstride, dst, c->stream, &sig), "systematic launch"))
-      return false;
-  } else if (all_systematic) {
+    return finish(
+        hip_check(launch_systematic_tiny(p, c->h_in, sl, dstride, dst, c->stream, &sig), "systematic launch"));
+  if (all_systematic) {
     // every systematic shard is present: decode == interleave (exact)
     // (one payload: no tile counter, systematic_w's static schedule)
-    if (!hip_check(launch_systematic(p, src, sl, dstride, 1, dst, out_bytes, nullptr, c->stream, &sig),
-                   "systematic launch"))
-      return false;
-  } else {
-    // the pattern's locator: computed once per device, then reused (§8f row 3)
-    std::shared_ptr<const Locator> loc = cached_locator(d, p, present, c->stream);
-    if (!loc) return false;
-    // on every path below `loc` is dropped only after the stream finished (the
-    // cache recycles entries nobody holds, and uses an entry's event only
-    // while it is not done: ec_runtime.hpp)
-    const auto release = [&](bool ok) {
-      // a failed synchronisation may mean the locator kernel itself faulted:
-      // the entry leaves the cache instead of being marked done, so no later
-      // hit skips the event wait and reads d_elog that was never written
-      if (!ok && hipStreamSynchronize(c->stream) != hipSuccess) locator_drop(d, *loc);
-      else locator_done(d, *loc);
-      return ok;
-    };
-    ScratchLease lease(d, reconstruct_scratch_bytes(p, sl, 1), c->stream);
-    if (!lease.ok()) return release(false);
-    void *scratch = lease.ptr();
-    const bool launched = hip_check(launch_reconstruct(p, device_tables(d), src, sl, dstride,
-                                                       loc->d_present, loc->d_elog, nullptr, 1,
-                                                       dst, out_bytes, scratch, c->stream),
-                                    "reconstruct launch");
-    const bool copied = launched && (direct || hip_check(hipMemcpyAsync(c->h_out, c->d_out, out_bytes,
-                                                                        hipMemcpyDeviceToHost, c->stream),
-                                                         "D2H"));
-    // Kernels only (direct): the signal-kernel wait; after a D2H copy the
-    // copy-to-kernel hand-off makes that slower than waiting on the stream
-    // 
-    const bool synced = (launched && copied) &&
-                        (direct ? finish_call(c, "reconstruct", &sig)
-                                : hip_check(hipStreamSynchronize(c->stream), "reconstruct"));
-    return release(launched && copied && synced);
+    const SysCall call{src, sl, dstride, 1, dst, out_bytes};
+    return finish(hip_check(launch_systematic(p, call, nullptr, c->stream, &sig), "systematic launch"));
   }
-  return (direct || hip_check(hipMemcpyAsync(c->h_out, c->d_out, out_bytes, hipMemcpyDeviceToHost,
-                                             c->stream),
-                              "D2H")) &&
-         (direct ? finish_call(c, "reconstruct", &sig)
-                 : hip_check(hipStreamSynchronize(c->stream), "reconstruct"));
+  // the pattern's locator: computed once per device, then reused (§8f row 3)
+  std::shared_ptr<const Locator> loc = cached_locator(d, p, present, c->stream);
+  if (!loc) return false;
+  // on every path below `loc` is dropped only after the stream finished (the
+  // cache recycles entries nobody holds, and uses an entry's event only
+  // while it is not done: ec_runtime.hpp)
+  const auto release = [&](bool ok) {
+    // a failed synchronisation may mean the locator kernel itself faulted:
+    // the entry leaves the cache instead of being marked done, so no later
+    // hit skips the event wait and reads d_elog that was never written
+    if (!ok && hipStreamSynchronize(c->stream) != hipSuccess) locator_drop(d, *loc);
+    else locator_done(d, *loc);
+    return ok;
+  };
+  ScratchLease lease(d, reconstruct_scratch_bytes(p, sl, 1), c->stream);
+  if (!lease.ok()) return release(false);
+  const ReconCall call{src, sl, dstride, loc->d_present, loc->d_elog, nullptr, 1, dst, out_bytes};
+  return release(finish(
+      hip_check(launch_reconstruct(p, device_tables(d), call, lease.ptr(), c->stream), "reconstruct launch")));
 }
 
 bool take_output(HostCtx *c, size_t bytes, DataBlock *out) {
@@ -355,7 +323,7 @@ NPRSResult ECCR_reconstruct_from_systematic(unsigned long nv, const ChunksList *
   pk.nv = p.k;  // staged layout holds only the k systematic shards
   if (!hip_check(hipMemcpyAsync(c->d_in, c->h_in, in_bytes, hipMemcpyHostToDevice, c->stream),
                  "H2D") ||
-      !hip_check(launch_systematic(pk, c->d_in, used, pitch, 1, c->d_out, out_bytes, nullptr, c->stream),
+      !hip_check(launch_systematic(pk, SysCall{c->d_in, used, pitch, 1, c->d_out, out_bytes}, nullptr, c->stream),
                  "systematic launch") ||
       !hip_check(hipMemcpyAsync(c->h_out, c->d_out, out_bytes, hipMemcpyDeviceToHost, c->stream),
                  "D2H") ||
@@ -438,6 +406,30 @@ NPRSResult ECCR_AMD_init_device(void) {
 }  // extern "C"
 
 namespace {
+// The one test of a caller's workspace: there, large enough, and (align = 256)
+// on the alignment every kernel's scratch layout assumes.  What follows from a
+// workspace that does not fit differs by call, on purpose:
+//
+// | call                                | short or NULL workspace  | large enough, not 256-B aligned |
+// |-------------------------------------|--------------------------|---------------------------------|
+// | encode_batch_ws, optional-counter   | static schedule, OK      | error UNKNOWN_CODE_PARAM (the   |
+// |   shapes (encode_scratch_optional)  |                          |   alignment is not part of      |
+// |                                     |                          |   "optional": align = 1 there)  |
+// | encode_batch_ws, other shapes       | error                    | error                           |
+// | reconstruct_batch_ws, and           | error                    | error                           |
+// |   error_locator_ws with need > 0    |                          |                                 |
+// | systematic_batch_ws                 | static schedule, OK      | static schedule, OK             |
+// | ragged *_ws                         | error, before the device | the same                        |
+// |                                     |   is touched             |                                 |
+bool workspace_fits(const Workspace &ws, size_t need, size_t align = 256) {
+  return ws.ptr && ws.bytes >= need && reinterpret_cast<uintptr_t>(ws.ptr) % align == 0;
+}
+
+void workspace_error(const Workspace &ws, size_t need, const char *needs) {
+  set_error("erasure_coding_crust(amd): workspace of " + std::to_string(ws.bytes) +
+            " bytes (256-B aligned required) is below the " + std::to_string(need) + " bytes this " + needs);
+}
+
 // Device scratch of one batch call: the caller's workspace (the *_ws entry
 // points) or else the scratch private to the call's stream (stream_scratch).
 // Either way, once the shape has run once on the stream, the call allocates,
@@ -457,10 +449,8 @@ struct BatchScratch {
       lease.emplace(d, s, need);
       p = lease->ptr();
       ok = lease->ok();
-    } else if (!ws->ptr || ws->bytes < need || reinterpret_cast<uintptr_t>(ws->ptr) % 256 != 0) {
-      set_error("erasure_coding_crust(amd): workspace of " + std::to_string(ws->bytes) +
-                " bytes (256-B aligned required) is below the " + std::to_string(need) +
-                " bytes this shape needs (ECCR_AMD_*_workspace_bytes)");
+    } else if (!workspace_fits(*ws, need)) {
+      workspace_error(*ws, need, "shape needs (ECCR_AMD_*_workspace_bytes)");
     } else {
       ok = true;
       p = ws->ptr;
@@ -475,26 +465,40 @@ size_t locator_scratch_bytes(const CodeParams &p, size_t batch) {
                                                      : (batch * 4 + 255) / 256 * 256 + dedup_scratch_bytes(batch);
 }
 
-NPRSResult encode_batch(unsigned long nv, const uint8_t *d_payloads, unsigned long plen,
-                        unsigned long pstride, unsigned long batch, uint8_t *d_shards,
-                        unsigned long sstride, hipStream_t s, const Workspace *ws) {
+// What a batch call is refused for before anything else is looked at, one
+// predicate per kind: the batch function and the ECCR_AMD_*_kernel diagnostic
+// of the kind share it.  NPRS_RESULT_OK: the call is well formed.
+NPRSResult_Tag encode_call_tag(const CodeParams &p, const EncodeCall &c) {
+  return c.plen == 0 || c.sstride < shard_len(p.k, c.plen) || c.pstride < c.plen ? NPRS_RESULT_BAD_PAYLOAD
+                                                                                 : NPRS_RESULT_OK;
+}
+NPRSResult_Tag recon_call_tag(const CodeParams &p, const ReconCall &c) {
+  if (c.slen % 2 != 0) return NPRS_RESULT_UNEVEN_LENGTH;
+  return c.sstride < c.slen || c.ostride < c.slen * p.k ? NPRS_RESULT_NON_UNIFORM_CHUNKS : NPRS_RESULT_OK;
+}
+// (the recovery moves whole symbols: once the pitches are checked against the
+// stated length, the call goes on with an odd trailing byte dropped)
+NPRSResult_Tag sys_call_tag(const CodeParams &p, SysCall *c) {
+  if (c->sstride < c->slen || c->ostride < c->slen / 2 * 2 * p.k) return NPRS_RESULT_NON_UNIFORM_CHUNKS;
+  c->slen = c->slen / 2 * 2;
+  return NPRS_RESULT_OK;
+}
+
+NPRSResult encode_batch(unsigned long nv, const EncodeCall &c, hipStream_t s, const Workspace *ws) {
   CodeParams p;
   NPRSResult r = params_or_error(nv, &p);
   if (r.tag != NPRS_RESULT_OK) return r;
-  if (plen == 0) return result(NPRS_RESULT_BAD_PAYLOAD);
-  if (sstride < shard_len(p.k, plen) || pstride < plen) return result(NPRS_RESULT_BAD_PAYLOAD);
+  if (const NPRSResult_Tag t = encode_call_tag(p, c); t != NPRS_RESULT_OK) return result(t);
   DeviceState *d = device_state();
   if (!d) return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
   // a workspace below the queried size (e.g. a size of 0 cached from an older
   // release) runs the shapes whose scratch is only a tile counter on the
   // static schedule: slower, not an error
-  const bool optional = ws && (!ws->ptr || ws->bytes < encode_scratch_bytes(p, plen, batch)) &&
-                        encode_scratch_optional(p);
-  BatchScratch sc(d, optional ? 0 : encode_scratch_bytes(p, plen, batch), s, ws);
+  const size_t need = encode_scratch_bytes(p, c.plen, c.batch);
+  const bool optional = ws && encode_scratch_optional(p) && !workspace_fits(*ws, need, 1);
+  BatchScratch sc(d, optional ? 0 : need, s, ws);
   if (!sc.ok) return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
-  if (!hip_check(launch_encode(p, device_tables(d), d_payloads, plen, pstride, batch, d_shards,
-                               sstride, sc.p, s),
-                 "encode launch"))
+  if (!hip_check(launch_encode(p, device_tables(d), c, sc.p, s), "encode launch"))
     return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
   return result(NPRS_RESULT_OK);
 }
@@ -528,23 +532,34 @@ NPRSResult error_locator(unsigned long nv, const uint8_t *d_present, unsigned lo
   return result(NPRS_RESULT_OK);
 }
 
-NPRSResult reconstruct_batch(unsigned long nv, const uint8_t *d_shards, unsigned long slen,
-                             unsigned long sstride, const uint8_t *d_present,
-                             const uint16_t *d_err_log, const uint32_t *d_pattern,
-                             unsigned long batch, uint8_t *d_out, unsigned long ostride,
-                             hipStream_t s, const Workspace *ws) {
+NPRSResult reconstruct_batch(unsigned long nv, const ReconCall &c, hipStream_t s, const Workspace *ws) {
   CodeParams p;
   NPRSResult r = params_or_error(nv, &p);
   if (r.tag != NPRS_RESULT_OK) return r;
-  if (slen % 2 != 0) return result(NPRS_RESULT_UNEVEN_LENGTH);
-  if (sstride < slen || ostride < slen * p.k) return result(NPRS_RESULT_NON_UNIFORM_CHUNKS);
+  if (const NPRSResult_Tag t = recon_call_tag(p, c); t != NPRS_RESULT_OK) return result(t);
   DeviceState *d = device_state();
   if (!d) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
-  BatchScratch sc(d, reconstruct_scratch_bytes(p, slen, batch), s, ws);
+  BatchScratch sc(d, reconstruct_scratch_bytes(p, c.slen, c.batch), s, ws);
   if (!sc.ok) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
-  if (!hip_check(launch_reconstruct(p, device_tables(d), d_shards, slen, sstride, d_present,
-                                    d_err_log, d_pattern, batch, d_out, ostride, sc.p, s),
-                 "reconstruct launch"))
+  if (!hip_check(launch_reconstruct(p, device_tables(d), c, sc.p, s), "reconstruct launch"))
+    return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
+  return result(NPRS_RESULT_OK);
+}
+
+// The scratch is systematic_w's tile counter only: a workspace that does not
+// fit (NULL, short or misaligned) runs the static schedule.
+NPRSResult systematic_batch(unsigned long nv, SysCall c, hipStream_t s, const Workspace *ws) {
+  CodeParams p;
+  NPRSResult r = params_or_error(nv, &p);
+  if (r.tag != NPRS_RESULT_OK) return r;
+  if (const NPRSResult_Tag t = sys_call_tag(p, &c); t != NPRS_RESULT_OK) return result(t);
+  DeviceState *d = device_state();
+  if (!d) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
+  const size_t need = choose_systematic(p, c, false) == Kernel::systematic_w ? systematic_scratch_bytes(p) : 0;
+  const bool skip = ws && !workspace_fits(*ws, need);
+  BatchScratch sc(d, skip ? 0 : need, s, ws);
+  if (!sc.ok) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
+  if (!hip_check(launch_systematic(p, c, sc.p, s), "systematic launch"))
     return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
   return result(NPRS_RESULT_OK);
 }
@@ -553,8 +568,6 @@ NPRSResult reconstruct_batch(unsigned long nv, const uint8_t *d_shards, unsigned
 // here, before anything is launched and before the device is touched; the
 // items live on the device and are validated there (the plan kernel).
 static_assert(sizeof(ECCR_AMD_RaggedItem) == sizeof(RaggedItem) && sizeof(RaggedItem) == 40, "item layout");
-
-bool aligned16(const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 // batch and the stated maximum: a count the 32-bit item indices and tile
 // tickets can hold.  tiles_of_max: tiles of the longest item the call allows.
@@ -579,144 +592,114 @@ NPRSResult ragged_counts(const char *what, unsigned long batch, unsigned long ma
   return result(NPRS_RESULT_OK);
 }
 
-// a ragged call always needs its workspace (the plan lives in it): checked
-// without a device, nothing launched on failure
-bool ragged_workspace_ok(const Workspace &ws, size_t need) {
-  if (ws.ptr && ws.bytes >= need && reinterpret_cast<uintptr_t>(ws.ptr) % 256 == 0) return true;
-  set_error("erasure_coding_crust(amd): workspace of " + std::to_string(ws.bytes) +
-            " bytes (256-B aligned required) is below the " + std::to_string(need) +
-            " bytes this ragged call needs (ECCR_AMD_*_ragged_workspace_bytes)");
-  return false;
+// What tells the three ragged calls apart; ragged_call is the rest.
+struct RaggedBuffer {
+  const void *ptr = nullptr;
+  unsigned align = 1;
+  bool required = false;  // NULL refused (the others are nullable)
+};
+struct RaggedKind {
+  const char *what;                    // the call's name in messages
+  RaggedBuffer bufs[7];                // its buffers with the alignment each needs (unused slots pass)
+  const char *alignment;               // the message's words for those
+  size_t tiles_of_max;                 // tile tickets of the longest item the call allows
+  NPRSResult_Tag empty_tag, fail_tag;  // a maximum of 0 / a workspace, device or launch failure
+  size_t need;                         // workspace bytes (a ragged call always has one: the plan lives in it)
+  const char *launching;               // hip_check's words for the launch
+};
+
+// The sequence of every ragged call, in this order: NULL buffers, the counts,
+// the alignments, the caller's workspace (all without a device: nothing is
+// launched on failure), then the device, the scratch and the launch.
+template <typename Launch>
+NPRSResult ragged_call(const RaggedKind &k, const RaggedCall &c, hipStream_t s, const Workspace *ws, Launch launch) {
+  const std::string what = std::string("erasure_coding_crust(amd): ") + k.what;
+  for (const RaggedBuffer &b : k.bufs)
+    if (b.required && !b.ptr) {
+      set_error(what + ": a NULL buffer");
+      return result(NPRS_RESULT_BAD_PAYLOAD);
+    }
+  const NPRSResult r = ragged_counts(k.what, c.batch, c.max_len, k.tiles_of_max, k.empty_tag);
+  if (r.tag != NPRS_RESULT_OK) return r;
+  for (const RaggedBuffer &b : k.bufs)
+    if (reinterpret_cast<uintptr_t>(b.ptr) % b.align != 0) {
+      set_error(what + ": " + k.alignment);
+      return result(NPRS_RESULT_BAD_PAYLOAD);
+    }
+  if (ws && !workspace_fits(*ws, k.need)) {
+    workspace_error(*ws, k.need, "ragged call needs (ECCR_AMD_*_ragged_workspace_bytes)");
+    return result(k.fail_tag);
+  }
+  DeviceState *d = device_state();
+  if (!d) return result(k.fail_tag);
+  BatchScratch sc(d, k.need, s, ws);
+  if (!sc.ok || !hip_check(launch(d, sc.p), k.launching)) return result(k.fail_tag);
+  return result(NPRS_RESULT_OK);
 }
 
-NPRSResult encode_ragged(unsigned long nv, const uint8_t *d_payloads, const ECCR_AMD_RaggedItem *d_items,
-                         unsigned long batch, unsigned long max_plen, uint8_t *d_shards, uint32_t *d_status,
-                         hipStream_t s, const Workspace *ws) {
+NPRSResult encode_ragged(unsigned long nv, const RaggedCall &c, hipStream_t s, const Workspace *ws) {
   CodeParams p;
   NPRSResult r = params_or_error(nv, &p);
   if (r.tag != NPRS_RESULT_OK) return r;
-  if (!d_payloads || !d_items || !d_shards) {
-    set_error("erasure_coding_crust(amd): encode_ragged: a NULL buffer");
-    return result(NPRS_RESULT_BAD_PAYLOAD);
-  }
   const size_t tile = ragged_encode_tile(p);
-  r = ragged_counts("encode_ragged", batch, max_plen, (shard_len(p.k, max_plen) / 2 + tile - 1) / tile,
-                    NPRS_RESULT_BAD_PAYLOAD);
-  if (r.tag != NPRS_RESULT_OK) return r;
-  if (!aligned16(d_payloads) || !aligned16(d_shards) || reinterpret_cast<uintptr_t>(d_items) % 8 != 0 ||
-      reinterpret_cast<uintptr_t>(d_status) % 4 != 0) {
-    set_error("erasure_coding_crust(amd): encode_ragged: d_payloads and d_shards must be 16-B aligned, d_items 8-B");
-    return result(NPRS_RESULT_BAD_PAYLOAD);
-  }
-  const size_t need = ragged_encode_workspace_bytes(p, batch, max_plen);
-  if (ws && !ragged_workspace_ok(*ws, need)) return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
-  DeviceState *d = device_state();
-  if (!d) return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
-  BatchScratch sc(d, need, s, ws);
-  if (!sc.ok) return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
-  if (!hip_check(launch_encode_ragged(p, device_tables(d), d_payloads, reinterpret_cast<const RaggedItem *>(d_items),
-                                      batch, max_plen, d_shards, d_status, sc.p, s),
-                 "ragged encode launch"))
-    return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
-  return result(NPRS_RESULT_OK);
+  const RaggedKind k{"encode_ragged",
+                     {{c.in, 16, true}, {c.items, 8, true}, {c.out, 16, true}, {c.status, 4, false}},
+                     "d_payloads and d_shards must be 16-B aligned, d_items 8-B",
+                     (shard_len(p.k, c.max_len) / 2 + tile - 1) / tile,
+                     NPRS_RESULT_BAD_PAYLOAD,
+                     NPRS_RESULT_UNKNOWN_CODE_PARAM,
+                     ragged_encode_workspace_bytes(p, c.batch, c.max_len),
+                     "ragged encode launch"};
+  return ragged_call(k, c, s, ws,
+                     [&](DeviceState *d, void *w) { return launch_encode_ragged(p, device_tables(d), c, w, s); });
 }
 
-NPRSResult reconstruct_ragged(unsigned long nv, const uint8_t *d_shards, const ECCR_AMD_RaggedItem *d_items,
-                              const uint8_t *d_present, const uint16_t *d_err_log, const uint32_t *d_pattern,
-                              unsigned long batch, unsigned long max_slen, uint8_t *d_out, uint32_t *d_status,
-                              hipStream_t s, const Workspace *ws) {
+NPRSResult reconstruct_ragged(unsigned long nv, const RaggedCall &c, hipStream_t s, const Workspace *ws) {
   CodeParams p;
   NPRSResult r = params_or_error(nv, &p);
   if (r.tag != NPRS_RESULT_OK) return r;
-  if (!d_shards || !d_items || !d_present || !d_err_log || !d_out) {
-    set_error("erasure_coding_crust(amd): reconstruct_ragged: a NULL buffer");
-    return result(NPRS_RESULT_BAD_PAYLOAD);
-  }
   const size_t tile = ragged_reconstruct_tile(p);
-  r = ragged_counts("reconstruct_ragged", batch, max_slen, (max_slen / 2 + tile - 1) / tile,
-                    NPRS_RESULT_NON_UNIFORM_CHUNKS);
-  if (r.tag != NPRS_RESULT_OK) return r;
   // (the n = 1024 kernel reads a pattern's flag and locator rows with vector loads)
-  if (!aligned16(d_shards) || !aligned16(d_out) || !aligned16(d_present) || !aligned16(d_err_log) ||
-      reinterpret_cast<uintptr_t>(d_items) % 8 != 0 || reinterpret_cast<uintptr_t>(d_pattern) % 4 != 0 ||
-      reinterpret_cast<uintptr_t>(d_status) % 4 != 0) {
-    set_error(
-        "erasure_coding_crust(amd): reconstruct_ragged: d_shards, d_out, d_present and d_err_log must be 16-B "
-        "aligned, d_items 8-B");
-    return result(NPRS_RESULT_BAD_PAYLOAD);
-  }
-  const size_t need = ragged_reconstruct_workspace_bytes(p, batch, max_slen);
-  if (ws && !ragged_workspace_ok(*ws, need)) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
-  DeviceState *d = device_state();
-  if (!d) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
-  BatchScratch sc(d, need, s, ws);
-  if (!sc.ok) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
-  if (!hip_check(launch_reconstruct_ragged(p, device_tables(d), d_shards, reinterpret_cast<const RaggedItem *>(d_items),
-                                           d_present, d_err_log, d_pattern, batch, max_slen, d_out, d_status, sc.p,
-                                           s),
-                 "ragged reconstruct launch"))
-    return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
-  return result(NPRS_RESULT_OK);
+  const RaggedKind k{"reconstruct_ragged",
+                     {{c.in, 16, true},
+                      {c.items, 8, true},
+                      {c.present, 16, true},
+                      {c.err_log, 16, true},
+                      {c.out, 16, true},
+                      {c.pattern, 4, false},
+                      {c.status, 4, false}},
+                     "d_shards, d_out, d_present and d_err_log must be 16-B aligned, d_items 8-B",
+                     (c.max_len / 2 + tile - 1) / tile,
+                     NPRS_RESULT_NON_UNIFORM_CHUNKS,
+                     NPRS_RESULT_UNKNOWN_RECONSTRUCTION,
+                     ragged_reconstruct_workspace_bytes(p, c.batch, c.max_len),
+                     "ragged reconstruct launch"};
+  return ragged_call(k, c, s, ws,
+                     [&](DeviceState *d, void *w) { return launch_reconstruct_ragged(p, device_tables(d), c, w, s); });
 }
 
-// The scratch is systematic_w's tile counter only: a NULL or short workspace
-// runs the static schedule, as the encode's does (encode_batch).
-NPRSResult systematic_batch(unsigned long nv, const uint8_t *d_shards, unsigned long slen, unsigned long sstride,
-                            unsigned long batch, uint8_t *d_out, unsigned long ostride, hipStream_t s,
-                            const Workspace *ws) {
+NPRSResult systematic_ragged(unsigned long nv, const RaggedCall &c, hipStream_t s, const Workspace *ws) {
   CodeParams p;
   NPRSResult r = params_or_error(nv, &p);
   if (r.tag != NPRS_RESULT_OK) return r;
-  if (sstride < slen || ostride < slen / 2 * 2 * p.k) return result(NPRS_RESULT_NON_UNIFORM_CHUNKS);
-  DeviceState *d = device_state();
-  if (!d) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
-  const bool counter = choose_systematic(p, slen / 2 * 2, sstride, batch, reinterpret_cast<uintptr_t>(d_shards),
-                                         reinterpret_cast<uintptr_t>(d_out), ostride, false) == Kernel::systematic_w;
-  const size_t need = counter ? systematic_scratch_bytes(p) : 0;
-  const bool skip = ws && (!ws->ptr || ws->bytes < need || reinterpret_cast<uintptr_t>(ws->ptr) % 256 != 0);
-  BatchScratch sc(d, skip ? 0 : need, s, ws);
-  if (!sc.ok) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
-  if (!hip_check(launch_systematic(p, d_shards, slen / 2 * 2, sstride, batch, d_out, ostride, sc.p, s),
-                 "systematic launch"))
-    return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
-  return result(NPRS_RESULT_OK);
-}
-
-NPRSResult systematic_ragged(unsigned long nv, const uint8_t *d_shards, const ECCR_AMD_RaggedItem *d_items,
-                             unsigned long batch, unsigned long max_slen, uint8_t *d_out, uint32_t *d_status,
-                             hipStream_t s, const Workspace *ws) {
-  CodeParams p;
-  NPRSResult r = params_or_error(nv, &p);
-  if (r.tag != NPRS_RESULT_OK) return r;
-  if (!d_shards || !d_items || !d_out) {
-    set_error("erasure_coding_crust(amd): systematic_ragged: a NULL buffer");
-    return result(NPRS_RESULT_BAD_PAYLOAD);
-  }
   // tickets: column tiles x systematic_w's row blocks
   const size_t tile = ragged_systematic_tile(p);
-  const size_t row_blocks = choose_systematic_ragged(p) == RaggedKernel::systematic_w_ragged
-                                ? systematic_w_row_blocks(p)
-                                : 1;
-  r = ragged_counts("systematic_ragged", batch, max_slen, (max_slen / 2 + tile - 1) / tile * row_blocks,
-                    NPRS_RESULT_NON_UNIFORM_CHUNKS);
-  if (r.tag != NPRS_RESULT_OK) return r;
-  if (!aligned16(d_shards) || !aligned16(d_out) || reinterpret_cast<uintptr_t>(d_items) % 8 != 0 ||
-      reinterpret_cast<uintptr_t>(d_status) % 4 != 0) {
-    set_error("erasure_coding_crust(amd): systematic_ragged: d_shards and d_out must be 16-B aligned, d_items 8-B");
-    return result(NPRS_RESULT_BAD_PAYLOAD);
-  }
-  const size_t need = ragged_systematic_workspace_bytes(p, batch);
-  if (ws && !ragged_workspace_ok(*ws, need)) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
-  DeviceState *d = device_state();
-  if (!d) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
-  BatchScratch sc(d, need, s, ws);
-  if (!sc.ok) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
-  if (!hip_check(launch_systematic_ragged(p, reinterpret_cast<const uint8_t *>(d_shards),
-                                          reinterpret_cast<const RaggedItem *>(d_items), batch, max_slen, d_out,
-                                          d_status, sc.p, s),
-                 "ragged systematic launch"))
-    return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
-  return result(NPRS_RESULT_OK);
+  const size_t row_blocks =
+      choose_systematic_ragged(p) == RaggedKernel::systematic_w_ragged ? systematic_w_row_blocks(p) : 1;
+  const RaggedKind k{"systematic_ragged",
+                     {{c.in, 16, true}, {c.items, 8, true}, {c.out, 16, true}, {c.status, 4, false}},
+                     "d_shards and d_out must be 16-B aligned, d_items 8-B",
+                     (c.max_len / 2 + tile - 1) / tile * row_blocks,
+                     NPRS_RESULT_NON_UNIFORM_CHUNKS,
+                     NPRS_RESULT_UNKNOWN_RECONSTRUCTION,
+                     ragged_systematic_workspace_bytes(p, c.batch),
+                     "ragged systematic launch"};
+  return ragged_call(k, c, s, ws, [&](DeviceState *, void *w) { return launch_systematic_ragged(p, c, w, s); });
+}
+
+// the ABI's item pointer as the library's own type (the same 40 bytes)
+const RaggedItem *items_of(const ECCR_AMD_RaggedItem *d_items) {
+  return reinterpret_cast<const RaggedItem *>(d_items);
 }
 }  // namespace
 
@@ -725,8 +708,8 @@ extern "C" {
 NPRSResult ECCR_AMD_encode_batch(unsigned long nv, const uint8_t *d_payloads, unsigned long plen,
                                  unsigned long pstride, unsigned long batch, uint8_t *d_shards,
                                  unsigned long sstride, void *stream) {
-  return encode_batch(nv, d_payloads, plen, pstride, batch, d_shards, sstride,
-                      static_cast<hipStream_t>(stream), nullptr);
+  return encode_batch(nv, {d_payloads, plen, pstride, batch, d_shards, sstride}, static_cast<hipStream_t>(stream),
+                      nullptr);
 }
 
 unsigned long ECCR_AMD_encode_workspace_bytes(unsigned long nv, unsigned long plen,
@@ -741,8 +724,8 @@ NPRSResult ECCR_AMD_encode_batch_ws(unsigned long nv, const uint8_t *d_payloads,
                                     uint8_t *d_shards, unsigned long sstride, void *d_workspace,
                                     unsigned long workspace_bytes, void *stream) {
   const Workspace ws{d_workspace, workspace_bytes};
-  return encode_batch(nv, d_payloads, plen, pstride, batch, d_shards, sstride,
-                      static_cast<hipStream_t>(stream), &ws);
+  return encode_batch(nv, {d_payloads, plen, pstride, batch, d_shards, sstride}, static_cast<hipStream_t>(stream),
+                      &ws);
 }
 
 NPRSResult ECCR_AMD_error_locator(unsigned long nv, const uint8_t *d_present, unsigned long batch,
@@ -799,8 +782,8 @@ NPRSResult ECCR_AMD_reconstruct_batch_patterns(unsigned long nv, const uint8_t *
                                                const uint8_t *d_present, const uint16_t *d_err_log,
                                                const uint32_t *d_pattern, unsigned long batch,
                                                uint8_t *d_out, unsigned long ostride, void *stream) {
-  return reconstruct_batch(nv, d_shards, slen, sstride, d_present, d_err_log, d_pattern, batch,
-                           d_out, ostride, static_cast<hipStream_t>(stream), nullptr);
+  return reconstruct_batch(nv, {d_shards, slen, sstride, d_present, d_err_log, d_pattern, batch, d_out, ostride},
+                           static_cast<hipStream_t>(stream), nullptr);
 }
 
 unsigned long ECCR_AMD_reconstruct_workspace_bytes(unsigned long nv, unsigned long slen,
@@ -817,8 +800,8 @@ NPRSResult ECCR_AMD_reconstruct_batch_ws(unsigned long nv, const uint8_t *d_shar
                                          uint8_t *d_out, unsigned long ostride, void *d_workspace,
                                          unsigned long workspace_bytes, void *stream) {
   const Workspace ws{d_workspace, workspace_bytes};
-  return reconstruct_batch(nv, d_shards, slen, sstride, d_present, d_err_log, d_pattern, batch,
-                           d_out, ostride, static_cast<hipStream_t>(stream), &ws);
+  return reconstruct_batch(nv, {d_shards, slen, sstride, d_present, d_err_log, d_pattern, batch, d_out, ostride},
+                           static_cast<hipStream_t>(stream), &ws);
 }
 
 NPRSResult ECCR_AMD_reconstruct_batch(unsigned long nv, const uint8_t *d_shards,
@@ -834,10 +817,9 @@ const char *ECCR_AMD_encode_kernel(unsigned long nv, const uint8_t *d_payloads, 
                                    unsigned long pstride, unsigned long batch,
                                    const uint8_t *d_shards, unsigned long sstride) {
   CodeParams p;
-  if (code_params(nv, &p) != ParamError::kOk || plen == 0) return nullptr;
-  if (sstride < shard_len(p.k, plen) || pstride < plen) return nullptr;
-  return kernel_name(choose_encode(p, plen, pstride, batch, reinterpret_cast<uintptr_t>(d_payloads),
-                                   reinterpret_cast<uintptr_t>(d_shards), sstride));
+  const EncodeCall c{d_payloads, plen, pstride, batch, const_cast<uint8_t *>(d_shards), sstride};
+  if (code_params(nv, &p) != ParamError::kOk || encode_call_tag(p, c) != NPRS_RESULT_OK) return nullptr;
+  return kernel_name(choose_encode(p, c));
 }
 
 const char *ECCR_AMD_reconstruct_kernel(unsigned long nv, const uint8_t *d_shards,
@@ -846,13 +828,10 @@ const char *ECCR_AMD_reconstruct_kernel(unsigned long nv, const uint8_t *d_shard
                                         unsigned long batch, const uint8_t *d_out,
                                         unsigned long ostride) {
   CodeParams p;
-  if (code_params(nv, &p) != ParamError::kOk || slen % 2 != 0) return nullptr;
-  if (sstride < slen || ostride < slen * p.k) return nullptr;
-  const ReconOverrides &o = recon_overrides();
-  return kernel_name(choose_reconstruct(
-      p, slen, sstride, batch, reinterpret_cast<uintptr_t>(d_shards),
-      reinterpret_cast<uintptr_t>(d_present), reinterpret_cast<uintptr_t>(d_err_log),
-      reinterpret_cast<uintptr_t>(d_out), ostride, o.waves8, o.force_packed));
+  const ReconCall c{d_shards, slen, sstride, d_present, d_err_log, nullptr, batch, const_cast<uint8_t *>(d_out),
+                    ostride};
+  if (code_params(nv, &p) != ParamError::kOk || recon_call_tag(p, c) != NPRS_RESULT_OK) return nullptr;
+  return kernel_name(choose_reconstruct(p, c, recon_overrides()));
 }
 
 int ECCR_AMD_reconstruct_n1024x_waves(unsigned long slen) { return n1024x_waves(slen); }
@@ -867,7 +846,7 @@ NPRSResult ECCR_AMD_locator_cache_stats(unsigned long *hits, unsigned long *miss
 NPRSResult ECCR_AMD_systematic_batch(unsigned long nv, const uint8_t *d_shards, unsigned long slen,
                                      unsigned long sstride, unsigned long batch, uint8_t *d_out,
                                      unsigned long ostride, void *stream) {
-  return systematic_batch(nv, d_shards, slen, sstride, batch, d_out, ostride, static_cast<hipStream_t>(stream),
+  return systematic_batch(nv, {d_shards, slen, sstride, batch, d_out, ostride}, static_cast<hipStream_t>(stream),
                           nullptr);
 }
 
@@ -882,7 +861,7 @@ NPRSResult ECCR_AMD_systematic_batch_ws(unsigned long nv, const uint8_t *d_shard
                                         unsigned long ostride, void *d_workspace, unsigned long workspace_bytes,
                                         void *stream) {
   const Workspace ws{d_workspace, workspace_bytes};
-  return systematic_batch(nv, d_shards, slen, sstride, batch, d_out, ostride, static_cast<hipStream_t>(stream),
+  return systematic_batch(nv, {d_shards, slen, sstride, batch, d_out, ostride}, static_cast<hipStream_t>(stream),
                           &ws);
 }
 
@@ -890,17 +869,16 @@ const char *ECCR_AMD_systematic_kernel(unsigned long nv, const uint8_t *d_shards
                                        unsigned long sstride, unsigned long batch, const uint8_t *d_out,
                                        unsigned long ostride) {
   CodeParams p;
-  if (code_params(nv, &p) != ParamError::kOk) return nullptr;
-  if (sstride < slen || ostride < slen / 2 * 2 * p.k) return nullptr;
-  return kernel_name(choose_systematic(p, slen / 2 * 2, sstride, batch, reinterpret_cast<uintptr_t>(d_shards),
-                                       reinterpret_cast<uintptr_t>(d_out), ostride, false));
+  SysCall c{d_shards, slen, sstride, batch, const_cast<uint8_t *>(d_out), ostride};
+  if (code_params(nv, &p) != ParamError::kOk || sys_call_tag(p, &c) != NPRS_RESULT_OK) return nullptr;
+  return kernel_name(choose_systematic(p, c, false));
 }
 
 NPRSResult ECCR_AMD_systematic_ragged(unsigned long nv, const uint8_t *d_shards, const ECCR_AMD_RaggedItem *d_items,
                                       unsigned long batch, unsigned long max_slen, uint8_t *d_out,
                                       uint32_t *d_status, void *stream) {
-  return systematic_ragged(nv, d_shards, d_items, batch, max_slen, d_out, d_status, static_cast<hipStream_t>(stream),
-                           nullptr);
+  return systematic_ragged(nv, {d_shards, items_of(d_items), batch, max_slen, d_out, d_status},
+                           static_cast<hipStream_t>(stream), nullptr);
 }
 
 NPRSResult ECCR_AMD_systematic_ragged_ws(unsigned long nv, const uint8_t *d_shards,
@@ -908,8 +886,8 @@ NPRSResult ECCR_AMD_systematic_ragged_ws(unsigned long nv, const uint8_t *d_shar
                                          unsigned long max_slen, uint8_t *d_out, uint32_t *d_status,
                                          void *d_workspace, unsigned long workspace_bytes, void *stream) {
   const Workspace ws{d_workspace, workspace_bytes};
-  return systematic_ragged(nv, d_shards, d_items, batch, max_slen, d_out, d_status, static_cast<hipStream_t>(stream),
-                           &ws);
+  return systematic_ragged(nv, {d_shards, items_of(d_items), batch, max_slen, d_out, d_status},
+                           static_cast<hipStream_t>(stream), &ws);
 }
 
 unsigned long ECCR_AMD_systematic_ragged_workspace_bytes(unsigned long nv, unsigned long batch,
@@ -928,7 +906,7 @@ const char *ECCR_AMD_systematic_ragged_kernel(unsigned long nv) {
 NPRSResult ECCR_AMD_encode_ragged(unsigned long nv, const uint8_t *d_payloads,
                                   const ECCR_AMD_RaggedItem *d_items, unsigned long batch,
                                   unsigned long max_plen, uint8_t *d_shards, uint32_t *d_status, void *stream) {
-  return encode_ragged(nv, d_payloads, d_items, batch, max_plen, d_shards, d_status,
+  return encode_ragged(nv, {d_payloads, items_of(d_items), batch, max_plen, d_shards, d_status},
                        static_cast<hipStream_t>(stream), nullptr);
 }
 
@@ -937,7 +915,7 @@ NPRSResult ECCR_AMD_encode_ragged_ws(unsigned long nv, const uint8_t *d_payloads
                                      unsigned long max_plen, uint8_t *d_shards, uint32_t *d_status,
                                      void *d_workspace, unsigned long workspace_bytes, void *stream) {
   const Workspace ws{d_workspace, workspace_bytes};
-  return encode_ragged(nv, d_payloads, d_items, batch, max_plen, d_shards, d_status,
+  return encode_ragged(nv, {d_payloads, items_of(d_items), batch, max_plen, d_shards, d_status},
                        static_cast<hipStream_t>(stream), &ws);
 }
 
@@ -946,8 +924,9 @@ NPRSResult ECCR_AMD_reconstruct_ragged(unsigned long nv, const uint8_t *d_shards
                                        const uint16_t *d_err_log, const uint32_t *d_pattern,
                                        unsigned long batch, unsigned long max_slen, uint8_t *d_out,
                                        uint32_t *d_status, void *stream) {
-  return reconstruct_ragged(nv, d_shards, d_items, d_present, d_err_log, d_pattern, batch, max_slen, d_out,
-                            d_status, static_cast<hipStream_t>(stream), nullptr);
+  return reconstruct_ragged(
+      nv, {d_shards, items_of(d_items), batch, max_slen, d_out, d_status, d_present, d_err_log, d_pattern},
+      static_cast<hipStream_t>(stream), nullptr);
 }
 
 NPRSResult ECCR_AMD_reconstruct_ragged_ws(unsigned long nv, const uint8_t *d_shards,
@@ -957,8 +936,9 @@ NPRSResult ECCR_AMD_reconstruct_ragged_ws(unsigned long nv, const uint8_t *d_sha
                                           uint32_t *d_status, void *d_workspace,
                                           unsigned long workspace_bytes, void *stream) {
   const Workspace ws{d_workspace, workspace_bytes};
-  return reconstruct_ragged(nv, d_shards, d_items, d_present, d_err_log, d_pattern, batch, max_slen, d_out,
-                            d_status, static_cast<hipStream_t>(stream), &ws);
+  return reconstruct_ragged(
+      nv, {d_shards, items_of(d_items), batch, max_slen, d_out, d_status, d_present, d_err_log, d_pattern},
+      static_cast<hipStream_t>(stream), &ws);
 }
 
 unsigned long ECCR_AMD_encode_ragged_workspace_bytes(unsigned long nv, unsigned long batch,

@@ -309,21 +309,19 @@ __global__ void __launch_bounds__(THREADS) reconstruct_gen(
 }
 
 template <int L, int KB>
-hipError_t launch_l(const CodeParams &p, const DevTables &t, const uint8_t *d_shards, size_t slen,
-                    size_t sstride, const uint8_t *d_present, const uint16_t *d_err_log,
-                                    const uint32_t *d_pattern,
-                    size_t batch, uint8_t *d_out, size_t ostride, const uint32_t *order, hipStream_t s) {
+hipError_t launch_l(const CodeParams &p, const DevTables &t, const ReconCall &c, const uint32_t *order,
+                    hipStream_t s) {
   int cus = 0;
   if (const hipError_t e = prepare_kernel(reinterpret_cast<const void *>(&reconstruct_gen<L, KB>),
                                           LDS_BYTES, &cus);
       e != hipSuccess)
     return e;
   constexpr int TC = WAVES * 4 * (1024 >> L);
-  const size_t tiles = (slen / 2 + TC - 1) / TC * batch;
+  const size_t tiles = (c.slen / 2 + TC - 1) / TC * c.batch;
   const unsigned grid = unsigned(tiles < size_t(cus) ? tiles : size_t(cus));
-  hipLaunchKernelGGL((reconstruct_gen<L, KB>), dim3(grid), dim3(THREADS), LDS_BYTES, s, d_shards,
-                     uint64_t(slen), uint64_t(sstride), d_present, d_err_log, d_pattern, order, d_out,
-                     uint64_t(ostride), int(p.nv), int(p.k), uint32_t(batch), t);
+  hipLaunchKernelGGL((reconstruct_gen<L, KB>), dim3(grid), dim3(THREADS), LDS_BYTES, s, c.shards,
+                     uint64_t(c.slen), uint64_t(c.sstride), c.present, c.err_log, c.pattern, order, c.out,
+                     uint64_t(c.ostride), int(p.nv), int(p.k), uint32_t(c.batch), t);
   return hipGetLastError();
 }
 
@@ -335,21 +333,15 @@ bool decgen_applicable(const CodeParams &p) {  // the (n, k) instantiated below
          (p.n == 1024 && p.k == 128);
 }
 
-hipError_t launch_reconstruct_gen(const CodeParams &p, const DevTables &t,
-                                  const uint8_t *d_shards, size_t slen, size_t sstride,
-                                  const uint8_t *d_present, const uint16_t *d_err_log,
-                                  const uint32_t *d_pattern,
-                                  size_t batch, uint8_t *d_out, size_t ostride, void *scratch,
+hipError_t launch_reconstruct_gen(const CodeParams &p, const DevTables &t, const ReconCall &c, void *scratch,
                                   hipStream_t s) {
   if (!scratch) return hipErrorInvalidValue;
   uint32_t *order = static_cast<uint32_t *>(scratch);  // gather_order_bytes(p, batch)
-  if (const hipError_t e = launch_gather_order(p, d_present, d_err_log, d_pattern, batch, order, s);
+  if (const hipError_t e = launch_gather_order(p, c.present, c.err_log, c.pattern, c.batch, order, s);
       e != hipSuccess)
     return e;
-#define ECAMD_DG(Lv, KBv)                                                                   \
-  if (p.n == (1u << Lv) && p.k == (1u << KBv))                                             \
-    return launch_l<Lv, KBv>(p, t, d_shards, slen, sstride, d_present, d_err_log, d_pattern, batch, d_out, \
-                             ostride, order, s);
+#define ECAMD_DG(Lv, KBv) \
+  if (p.n == (1u << Lv) && p.k == (1u << KBv)) return launch_l<Lv, KBv>(p, t, c, order, s);
   // every (n, k) of 46 <= n_validators <= 765 (decgen_applicable)
   ECAMD_DG(6, 4)
   ECAMD_DG(7, 4)

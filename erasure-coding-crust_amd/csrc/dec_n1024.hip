@@ -496,14 +496,10 @@ static_assert(size_t(COLS) == kN1024Cols, "choose_reconstruct tests this tile");
 // packed (choose_reconstruct: fewer columns per payload than a tile, a shard
 // pitch / base the 16-B row loads cannot take, or the experiment override):
 // any even pitch and base, ncols4 * batch + COLS < 2^32
-hipError_t launch_reconstruct_n1024(const CodeParams &p, const DevTables &t, bool packed,
-                                    const uint8_t *d_shards, size_t slen, size_t sstride,
-                                    const uint8_t *d_present, const uint16_t *d_err_log,
-                                    const uint32_t *d_pattern,
-                                    size_t batch, uint8_t *d_out, size_t ostride, void *scratch,
-                                    hipStream_t s) {
+hipError_t launch_reconstruct_n1024(const CodeParams &p, const DevTables &t, bool packed, const ReconCall &c,
+                                    void *scratch, hipStream_t s) {
   int cus = 0;
-  const size_t ncols4 = (slen / 2 + 3) / 4 * 4;
+  const size_t ncols4 = (c.slen / 2 + 3) / 4 * 4;
   const void *fn = packed ? reinterpret_cast<const void *>(&reconstruct_n1024<true>)
                           : reinterpret_cast<const void *>(&reconstruct_n1024<false>);
   if (const hipError_t e = prepare_kernel(fn, LDS_BYTES, &cus); e != hipSuccess) return e;
@@ -511,22 +507,21 @@ hipError_t launch_reconstruct_n1024(const CodeParams &p, const DevTables &t, boo
   if (!packed) {  // the packed gather reads rows in natural order
     if (!scratch) return hipErrorInvalidValue;
     order = static_cast<uint32_t *>(scratch);  // gather_order_bytes(p, batch)
-    if (const hipError_t e = launch_gather_order(p, d_present, d_err_log, d_pattern, batch, order, s);
+    if (const hipError_t e = launch_gather_order(p, c.present, c.err_log, c.pattern, c.batch, order, s);
         e != hipSuccess)
       return e;
   }
-  const size_t tiles = packed ? ncols4 / 4 * batch : (slen / 2 + COLS - 1) / COLS * batch;  // packed: groups
+  const size_t tiles = packed ? ncols4 / 4 * c.batch : (c.slen / 2 + COLS - 1) / COLS * c.batch;  // packed: groups
   const unsigned grid = unsigned(tiles < size_t(cus) ? tiles : size_t(cus));
   if (packed)
-    hipLaunchKernelGGL(reconstruct_n1024<true>, dim3(grid), dim3(THREADS), LDS_BYTES, s, d_shards,
-                       uint64_t(slen), uint64_t(sstride), d_present, d_err_log, d_pattern, order,
-                       d_out, uint64_t(ostride), int(p.nv), uint32_t(batch), uint32_t(ncols4), t);
+    hipLaunchKernelGGL(reconstruct_n1024<true>, dim3(grid), dim3(THREADS), LDS_BYTES, s, c.shards,
+                       uint64_t(c.slen), uint64_t(c.sstride), c.present, c.err_log, c.pattern, order,
+                       c.out, uint64_t(c.ostride), int(p.nv), uint32_t(c.batch), uint32_t(ncols4), t);
   else
-    hipLaunchKernelGGL(reconstruct_n1024<false>, dim3(grid), dim3(THREADS), LDS_BYTES, s, d_shards,
-                       uint64_t(slen), uint64_t(sstride), d_present, d_err_log, d_pattern, order,
-                       d_out, uint64_t(ostride), int(p.nv), uint32_t(batch), uint32_t(ncols4), t);
+    hipLaunchKernelGGL(reconstruct_n1024<false>, dim3(grid), dim3(THREADS), LDS_BYTES, s, c.shards,
+                       uint64_t(c.slen), uint64_t(c.sstride), c.present, c.err_log, c.pattern, order,
+                       c.out, uint64_t(c.ostride), int(p.nv), uint32_t(c.batch), uint32_t(ncols4), t);
   return hipGetLastError();
 }
-
 
 }  // namespace ecamd

@@ -55,7 +55,7 @@ __global__ void __launch_bounds__(64 * WAVES) reconstruct_n1024x(
 // scratch of the n = 1024 reconstructs: the gather order, then the tile
 // counter of reconstruct_n1024x (256 B apart)
 size_t n1024_tick_offset(const CodeParams &p, size_t batch) { return (gather_order_bytes(p, batch) + 255) / 256 * 256; }
-size_t n1024_scratch_bytes(const CodeParams &p, size_t batch) { return n1024_tick_offset(p, batch) + 256; }
+size_t n1024_scratch_bytes(const CodeParams &p, size_t batch) { return n1024_tick_offset(p, batch) + kTileCounterBytes; }
 
 static_assert(size_t(Form<12>::COLS) == kN1024xMinCols, "choose_reconstruct: at least one whole tile");
 static_assert(size_t(Form<16>::COLS) <= kN1024x16MinCols, "n1024x_waves: at least one whole tile");
@@ -68,42 +68,32 @@ int n1024x_waves(size_t slen) {
 
 namespace {
 template <int WAVES>
-hipError_t launch_form(const CodeParams &p, const DevTables &t, const uint8_t *d_shards, size_t slen,
-                       size_t sstride, const uint8_t *d_present, const uint16_t *d_err_log,
-                       const uint32_t *d_pattern, size_t batch, uint8_t *d_out, size_t ostride,
-                       void *scratch, hipStream_t s) {
+hipError_t launch_form(const CodeParams &p, const DevTables &t, const ReconCall &c, void *scratch, hipStream_t s) {
   using F = Form<WAVES>;
   int cus = 0;
-  if (!t.cimg || !scratch || slen / 2 < size_t(F::COLS)) return hipErrorInvalidValue;
+  if (!t.cimg || !scratch || c.slen / 2 < size_t(F::COLS)) return hipErrorInvalidValue;
   if (const hipError_t e = prepare_kernel(reinterpret_cast<const void *>(&reconstruct_n1024x<WAVES>), F::LDS_BYTES, &cus);
       e != hipSuccess)
     return e;
-  const size_t tiles = (slen / 2 + F::COLS - 1) / F::COLS * batch;
+  const size_t tiles = (c.slen / 2 + F::COLS - 1) / F::COLS * c.batch;
   if (tiles + 4096 >= (size_t(1) << 32)) return hipErrorInvalidValue;  // 32-bit tile tickets
   uint32_t *order = static_cast<uint32_t *>(scratch);  // n1024_scratch_bytes(p, batch)
-  uint32_t *tick = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(scratch) + n1024_tick_offset(p, batch));
-  if (const hipError_t e = launch_gather_order(p, d_present, d_err_log, d_pattern, batch, order, s);
+  uint32_t *tick = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(scratch) + n1024_tick_offset(p, c.batch));
+  if (const hipError_t e = launch_gather_order(p, c.present, c.err_log, c.pattern, c.batch, order, s);
       e != hipSuccess)
     return e;
   if (const hipError_t e = launch_zero_counters(tick, sizeof(uint32_t), s); e != hipSuccess) return e;
   const unsigned grid = unsigned(tiles < size_t(cus) ? tiles : size_t(cus));
-  hipLaunchKernelGGL(reconstruct_n1024x<WAVES>, dim3(grid), dim3(F::THREADS), F::LDS_BYTES, s, d_shards,
-                     uint64_t(slen), uint64_t(sstride), d_present, d_err_log, d_pattern, order, d_out,
-                     uint64_t(ostride), int(p.nv), uint32_t(batch), tick, t);
+  hipLaunchKernelGGL(reconstruct_n1024x<WAVES>, dim3(grid), dim3(F::THREADS), F::LDS_BYTES, s, c.shards,
+                     uint64_t(c.slen), uint64_t(c.sstride), c.present, c.err_log, c.pattern, order, c.out,
+                     uint64_t(c.ostride), int(p.nv), uint32_t(c.batch), tick, t);
   return hipGetLastError();
 }
 }  // namespace
 
-hipError_t launch_reconstruct_n1024x(const CodeParams &p, const DevTables &t,
-                                     const uint8_t *d_shards, size_t slen, size_t sstride,
-                                     const uint8_t *d_present, const uint16_t *d_err_log,
-                                     const uint32_t *d_pattern, size_t batch, uint8_t *d_out,
-                                     size_t ostride, void *scratch, hipStream_t s) {
-  return n1024x_waves(slen) == 16
-             ? launch_form<16>(p, t, d_shards, slen, sstride, d_present, d_err_log, d_pattern, batch, d_out,
-                               ostride, scratch, s)
-             : launch_form<12>(p, t, d_shards, slen, sstride, d_present, d_err_log, d_pattern, batch, d_out,
-                               ostride, scratch, s);
+hipError_t launch_reconstruct_n1024x(const CodeParams &p, const DevTables &t, const ReconCall &c, void *scratch,
+                                     hipStream_t s) {
+  return n1024x_waves(c.slen) == 16 ? launch_form<16>(p, t, c, scratch, s) : launch_form<12>(p, t, c, scratch, s);
 }
 
 }  // namespace ecamd

@@ -152,9 +152,8 @@ __global__ void __launch_bounds__(64 * kRaggedWaves) reconstruct_n1024x_ragged(
 // gather order follows the plan in it.  The grid is sized from the most tiles
 // the call can have (the host does not know the items): workgroups beyond the
 // real count take tickets past the end and leave.
-hipError_t launch_reconstruct_n1024x_ragged(const CodeParams &p, const DevTables &t, const uint8_t *d_present,
-                                            const uint16_t *d_err_log, const uint32_t *d_pattern, size_t batch,
-                                            size_t max_slen, void *ws, hipStream_t s) {
+hipError_t launch_reconstruct_n1024x_ragged(const CodeParams &p, const DevTables &t, const RaggedCall &c, void *ws,
+                                            hipStream_t s) {
   using F = Form<kRaggedWaves>;
   int cus = 0;
   if (!t.cimg || !ws) return hipErrorInvalidValue;
@@ -162,15 +161,15 @@ hipError_t launch_reconstruct_n1024x_ragged(const CodeParams &p, const DevTables
           prepare_kernel(reinterpret_cast<const void *>(&reconstruct_n1024x_ragged), F::LDS_BYTES, &cus);
       e != hipSuccess)
     return e;
-  const size_t most = (max_slen / 2 + F::COLS - 1) / F::COLS * batch;
+  const size_t most = (c.max_len / 2 + F::COLS - 1) / F::COLS * c.batch;
   if (most + 4096 >= (size_t(1) << 32)) return hipErrorInvalidValue;  // 32-bit tile tickets
-  uint32_t *order = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(ws) + ragged_scratch_offset(batch));
-  if (const hipError_t e = launch_gather_order(p, d_present, d_err_log, d_pattern, batch, order, s);
+  uint32_t *order = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(ws) + ragged_scratch_offset(c.batch));
+  if (const hipError_t e = launch_gather_order(p, c.present, c.err_log, c.pattern, c.batch, order, s);
       e != hipSuccess)
     return e;
   const unsigned grid = unsigned(most < size_t(cus) ? most : size_t(cus));
   hipLaunchKernelGGL(reconstruct_n1024x_ragged, dim3(grid), dim3(F::THREADS), F::LDS_BYTES, s, ragged_hdr(ws),
-                     d_present, d_err_log, d_pattern, order, ragged_tick(ws), t);
+                     c.present, c.err_log, c.pattern, order, ragged_tick(ws), t);
   return hipGetLastError();
 }
 

@@ -528,12 +528,9 @@ bool n4096_applicable(const CodeParams &p) {  // the (n, k) instantiated below
   return (p.n == 4096 && (p.k == 1024 || p.k == 512)) || (p.n == 2048 && (p.k == 512 || p.k == 256));
 }
 
-hipError_t launch_reconstruct_n4096(const CodeParams &p, const DevTables &t,
-                                    const uint8_t *d_shards, size_t slen, size_t sstride,
-                                    const uint8_t *d_present, const uint16_t *d_err_log,
-                                    const uint32_t *d_pattern,
-                                    size_t batch, uint8_t *d_out, size_t ostride, void *scratch,
+hipError_t launch_reconstruct_n4096(const CodeParams &p, const DevTables &t, const ReconCall &c, void *scratch,
                                     hipStream_t s) {
+  const size_t batch = c.batch;
   int cus = 0;
   const void *fn = nullptr;
   if (p.n == 4096) fn = p.k == 1024 ? reinterpret_cast<const void *>(&reconstruct_n4096<4, 10>)
@@ -543,24 +540,24 @@ hipError_t launch_reconstruct_n4096(const CodeParams &p, const DevTables &t,
   if (const hipError_t e = prepare_kernel(fn, LDS_BYTES, &cus); e != hipSuccess) return e;
   if (!scratch) return hipErrorInvalidValue;
   uint32_t *order = static_cast<uint32_t *>(scratch);  // n4096_scratch_bytes(p, batch)
-  if (const hipError_t e = launch_gather_order(p, d_present, d_err_log, d_pattern, batch, order, s);
+  if (const hipError_t e = launch_gather_order(p, c.present, c.err_log, c.pattern, batch, order, s);
       e != hipSuccess)
     return e;
   uint8_t *oimg = static_cast<uint8_t *>(scratch) + gather_order_bytes(p, batch);
-  hipLaunchKernelGGL(n4096_out_image, dim3(unsigned(batch)), dim3(256), 0, s, d_err_log, d_present, d_pattern,
+  hipLaunchKernelGGL(n4096_out_image, dim3(unsigned(batch)), dim3(256), 0, s, c.err_log, c.present, c.pattern,
                        int(p.n), int(p.nv), t.mtab_tout, oimg);  // tower in, symbols out
-  const size_t tiles = (slen / 2 + COLS - 1) / COLS * batch;
+  const size_t tiles = (c.slen / 2 + COLS - 1) / COLS * batch;
   if (tiles >= (size_t(1) << 32) - size_t(2) * cus) return hipErrorInvalidValue;
   uint32_t *tick = reinterpret_cast<uint32_t *>(oimg + batch * kOutImageBytes);  // the TileQueue counters
   if (const hipError_t e = launch_zero_counters(tick, kTileQueueBytes, s); e != hipSuccess) return e;
   const unsigned grid = unsigned(tiles < size_t(cus) ? tiles : size_t(cus));
   static const Lin lin4 = n4096_lin(4), lin2 = n4096_lin(2);
   if (lin4.p[0] == 0xDEAD || lin2.p[0] == 0xDEAD) return hipErrorInvalidValue;  // not subfield (never)
-#define ECAMD_D4(NQv, KBv)                                                                    \
-  if (p.n == 1024u * NQv && p.k == (1u << KBv))                                                  \
-    hipLaunchKernelGGL((reconstruct_n4096<NQv, KBv>), dim3(grid), dim3(THREADS), LDS_BYTES, s,   \
-                       d_shards, uint64_t(slen), uint64_t(sstride), d_present, d_err_log, d_pattern, order, d_out, \
-                       uint64_t(ostride), int(p.nv), uint32_t(p.k), uint32_t(batch), t,         \
+#define ECAMD_D4(NQv, KBv)                                                                           \
+  if (p.n == 1024u * NQv && p.k == (1u << KBv))                                                         \
+    hipLaunchKernelGGL((reconstruct_n4096<NQv, KBv>), dim3(grid), dim3(THREADS), LDS_BYTES, s,          \
+                       c.shards, uint64_t(c.slen), uint64_t(c.sstride), c.present, c.err_log, c.pattern, \
+                       order, c.out, uint64_t(c.ostride), int(p.nv), uint32_t(p.k), uint32_t(batch), t, \
                        NQv == 4 ? lin4 : lin2, oimg, tick);
   ECAMD_D4(4, 10)
   else ECAMD_D4(4, 9)

@@ -510,7 +510,40 @@ int groups_for(uint32_t size) {  // byte-planar groups per workgroup
   return int(g > 64 ? 64 : g);
 }
 
+// Launch geometry of the generic kernels (uniform and ragged, encode and
+// reconstruct) for a transform of `size` points over `positions` pieces /
+// shard positions per payload: G groups per workgroup, a tile of 4 G
+// positions per block of grid.x, the two transform buffers in LDS (shm bytes)
+// or, above kLdsSlots points, in global scratch.
+struct GenericGeo {
+  int G;
+  size_t tiles;
+  bool lds;
+  size_t shm;
+};
+GenericGeo generic_geo(uint32_t size, size_t positions) {
+  const int G = groups_for(size);
+  const bool lds = size <= uint32_t(kLdsSlots);
+  return {G, (positions + 4 * G - 1) / (4 * G), lds, lds ? 2 * size_t(size) * G * sizeof(uint2) : 0};
+}
+
+// blocks of systematic_g / systematic_g_ragged over the columns of the
+// (longest) item: grid-stride loops beyond 4096 blocks
+unsigned systematic_g_blocks(const CodeParams &p, size_t slen) {
+  const size_t blocks = (slen / 2 * p.k + kBlock - 1) / kBlock;
+  return unsigned(blocks > 4096 ? 4096 : blocks);
+}
+
 }  // namespace
+
+// The generic kernels' scratch: one pair of transform buffers per block of the
+// launch.  Needed only where size > kLdsSlots, and there groups_for is 1, so
+// the launch's tiles, (positions + 4 G - 1) / (4 G), are the (positions + 3) / 4
+// a size query has always answered with.
+size_t generic_scratch_bytes(uint32_t size, size_t positions, size_t batch) {
+  const GenericGeo g = generic_geo(size, positions);
+  return g.lds ? 0 : g.tiles * grid_y(batch) * 2 * size_t(size) * sizeof(uint2);
+}
 
 bool locator_wave_applicable(uint32_t n) { return n >= 64 && n <= 4096; }
 
@@ -539,14 +572,7 @@ bool encode_scratch_optional(const CodeParams &p) {
 }
 
 size_t encode_scratch_bytes(const CodeParams &p, size_t plen, size_t batch) {
-  if (k1024_applicable(p)) return k1024_scratch_bytes(plen, batch);
-  if (k256_applicable(p)) return k256_scratch_bytes(p);
-  if (k512w_applicable(p)) return k512w_scratch_bytes(p);
-  if (kw_applicable(p)) return kw_scratch_bytes(p);
-  if (p.k <= uint32_t(kLdsSlots)) return 0;
-  const size_t pieces = shard_len(p.k, plen) / 2;
-  const size_t tiles = (pieces + 3) / 4;
-  return tiles * grid_y(batch) * 2 * size_t(p.k) * sizeof(uint2);
+  return encode_scratch_optional(p) ? kTileCounterBytes : generic_scratch_bytes(p.k, shard_len(p.k, plen) / 2, batch);
 }
 
 const char *kernel_name(Kernel k) {
@@ -571,16 +597,15 @@ const char *kernel_name(Kernel k) {
 // flattened piece space (pieces rounded up to 8, per payload) stays below
 // 2^32; past that, or with an odd shard base or pitch, the shape goes on to
 // the kernels below.
-Kernel choose_encode(const CodeParams &p, size_t plen, size_t pstride, size_t batch,
-                     uintptr_t payloads, uintptr_t shards, size_t sstride) {
-  if (batch == 0 || plen == 0) return Kernel::invalid;
-  const bool aligned = payloads % 16 == 0 && shards % 8 == 0 && (batch == 1 || pstride % 16 == 0) &&
-                       sstride % 8 == 0;
+Kernel choose_encode(const CodeParams &p, const EncodeCall &c) {
+  if (c.batch == 0 || c.plen == 0) return Kernel::invalid;
+  const bool aligned = addr(c.payloads) % 16 == 0 && addr(c.shards) % 8 == 0 &&
+                       (c.batch == 1 || c.pstride % 16 == 0) && c.sstride % 8 == 0;
   if (k256_applicable(p)) {
-    const size_t npp = (plen + 2 * 256 - 1) / (2 * 256);  // pieces per payload
+    const size_t npp = (c.plen + 2 * 256 - 1) / (2 * 256);  // pieces per payload
     if (aligned && npp >= kK256Tile) return p.n == 1024 ? Kernel::encode_k256w : Kernel::encode_kw;
     const size_t npp8 = (npp + 7) / 8 * 8;  // (>= npp: also bounds the exactly flattened space of PK = 2)
-    if (shards % 2 == 0 && sstride % 2 == 0 && npp8 * batch + kK256Tile < (size_t(1) << 32))
+    if (addr(c.shards) % 2 == 0 && c.sstride % 2 == 0 && npp8 * c.batch + kK256Tile < (size_t(1) << 32))
       return Kernel::encode_k256_packed;
   }
   if (aligned && k512w_applicable(p)) return Kernel::encode_k512w;
@@ -589,36 +614,26 @@ Kernel choose_encode(const CodeParams &p, size_t plen, size_t pstride, size_t ba
   return Kernel::encode_g;
 }
 
-hipError_t launch_encode(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,
-                         size_t plen, size_t pstride, size_t batch, uint8_t *d_shards,
-                         size_t sstride, void *scratch, hipStream_t s, HostSig *sig) {
-  switch (choose_encode(p, plen, pstride, batch, reinterpret_cast<uintptr_t>(d_payloads),
-                        reinterpret_cast<uintptr_t>(d_shards), sstride)) {
-    case Kernel::encode_k256w:
-      return launch_encode_k256w(p, t, d_payloads, plen, pstride, batch, d_shards, sstride, scratch, s);
-    case Kernel::encode_k256_packed:
-      return launch_encode_k256(p, t, d_payloads, plen, pstride, batch, d_shards, sstride, s);
-    case Kernel::encode_kw:
-      return launch_encode_kw(p, t, d_payloads, plen, pstride, batch, d_shards, sstride, scratch, s);
-    case Kernel::encode_k512w:
-      return launch_encode_k512w(p, t, d_payloads, plen, pstride, batch, d_shards, sstride, scratch, s);
-    case Kernel::encode_k1024:
-      return launch_encode_k1024(p, t, d_payloads, plen, pstride, batch, d_shards, sstride, scratch, s);
+hipError_t launch_encode(const CodeParams &p, const DevTables &t, const EncodeCall &c, void *scratch,
+                         hipStream_t s, HostSig *sig) {
+  switch (choose_encode(p, c)) {
+    case Kernel::encode_k256w: return launch_encode_k256w(p, t, c, scratch, s);
+    case Kernel::encode_k256_packed: return launch_encode_k256(p, t, c, scratch, s);
+    case Kernel::encode_kw: return launch_encode_kw(p, t, c, scratch, s);
+    case Kernel::encode_k512w: return launch_encode_k512w(p, t, c, scratch, s);
+    case Kernel::encode_k1024: return launch_encode_k1024(p, t, c, scratch, s);
     case Kernel::encode_g: break;
     default: return hipSuccess;  // an empty call
   }
-  const size_t sl = shard_len(p.k, plen);
-  const int G = groups_for(p.k);
-  const size_t tiles = (sl / 2 + 4 * G - 1) / (4 * G);
-  const bool lds = p.k <= uint32_t(kLdsSlots);
-  const size_t shm = lds ? 2 * size_t(p.k) * G * sizeof(uint2) : 0;
-  dim3 grid((unsigned)tiles, (unsigned)grid_y(batch));
+  const size_t sl = shard_len(p.k, c.plen);
+  const GenericGeo g = generic_geo(p.k, sl / 2);
+  dim3 grid((unsigned)g.tiles, (unsigned)grid_y(c.batch));
   const bool fuse = sig && sig->flag && grid.x * grid.y == 1;
   if (fuse) sig->fused = true;
-  hipLaunchKernelGGL(encode_g, grid, dim3(kBlock), shm, s, d_payloads, uint64_t(plen),
-                     uint64_t(pstride), d_shards, uint64_t(sl), uint64_t(sstride), int(p.nv),
-                     ilog2(p.n), ilog2(p.k), ilog2(uint32_t(G)), uint32_t(batch), t,
-                     lds ? nullptr : static_cast<uint2 *>(scratch), fuse ? sig->flag : nullptr,
+  hipLaunchKernelGGL(encode_g, grid, dim3(kBlock), g.shm, s, c.payloads, uint64_t(c.plen),
+                     uint64_t(c.pstride), c.shards, uint64_t(sl), uint64_t(c.sstride), int(p.nv),
+                     ilog2(p.n), ilog2(p.k), ilog2(uint32_t(g.G)), uint32_t(c.batch), t,
+                     g.lds ? nullptr : static_cast<uint2 *>(scratch), fuse ? sig->flag : nullptr,
                      fuse ? sig->v : 0u);
   return hipGetLastError();
 }
@@ -697,9 +712,7 @@ size_t reconstruct_scratch_bytes(const CodeParams &p, size_t slen, size_t batch)
   if (n4096_applicable(p)) return n4096_scratch_bytes(p, batch);
   if (n1024_applicable(p)) return n1024_scratch_bytes(p, batch);
   if (decgen_applicable(p)) return gather_order_bytes(p, batch);
-  if (p.n <= uint32_t(kLdsSlots)) return 0;
-  const size_t tiles = (slen / 2 + 3) / 4;
-  return tiles * grid_y(batch) * 2 * size_t(p.n) * sizeof(uint2);
+  return generic_scratch_bytes(p.n, slen / 2, batch);
 }
 
 const ReconOverrides &recon_overrides() {
@@ -721,9 +734,9 @@ const ReconOverrides &recon_overrides() {
 // form for payloads under one tile of columns and for any even shard base and
 // pitch, while its flattened column space (columns rounded up to 4, per
 // payload) stays below 2^32: past that it launches nothing.
-Kernel choose_reconstruct(const CodeParams &p, size_t slen, size_t sstride, size_t batch,
-                          uintptr_t shards, uintptr_t present, uintptr_t err_log, uintptr_t out,
-                          size_t ostride, bool waves8, bool force_packed) {
+Kernel choose_reconstruct(const CodeParams &p, const ReconCall &c, const ReconOverrides &o) {
+  const size_t slen = c.slen, sstride = c.sstride, batch = c.batch, ostride = c.ostride;
+  const uintptr_t shards = addr(c.shards), present = addr(c.present), err_log = addr(c.err_log), out = addr(c.out);
   if (batch == 0 || slen < 2) return Kernel::invalid;
   const bool aligned = shards % 16 == 0 && out % 8 == 0 && sstride % 16 == 0 &&
                        (batch == 1 || ostride % 8 == 0);
@@ -733,9 +746,9 @@ Kernel choose_reconstruct(const CodeParams &p, size_t slen, size_t sstride, size
   const size_t ncols = slen / 2;
   if (n1024_applicable(p)) {
     const bool packed = ncols < kN1024Cols || shards % 16 != 0 || sstride % 16 != 0;
-    if (!packed && aligned && out8 && !waves8 && ncols >= kN1024xMinCols) return Kernel::reconstruct_n1024x;
+    if (!packed && aligned && out8 && !o.waves8 && ncols >= kN1024xMinCols) return Kernel::reconstruct_n1024x;
     if (packed ? out8 && shards % 2 == 0 && sstride % 2 == 0 : aligned && out8) {
-      if (!packed && !force_packed) return Kernel::reconstruct_n1024;
+      if (!packed && !o.force_packed) return Kernel::reconstruct_n1024;
       const size_t ncols4 = (ncols + 3) / 4 * 4;
       return ncols4 * batch + kN1024Cols < (size_t(1) << 32) ? Kernel::reconstruct_n1024_packed
                                                              : Kernel::invalid;
@@ -746,43 +759,26 @@ Kernel choose_reconstruct(const CodeParams &p, size_t slen, size_t sstride, size
   return Kernel::reconstruct_g;
 }
 
-hipError_t launch_reconstruct(const CodeParams &p, const DevTables &t, const uint8_t *d_shards,
-                              size_t slen, size_t sstride, const uint8_t *d_present,
-                              const uint16_t *d_err_log, const uint32_t *d_pattern, size_t batch,
-                              uint8_t *d_out, size_t ostride, void *scratch, hipStream_t s) {
-  const ReconOverrides &o = recon_overrides();
-  const Kernel kern = choose_reconstruct(
-      p, slen, sstride, batch, reinterpret_cast<uintptr_t>(d_shards),
-      reinterpret_cast<uintptr_t>(d_present), reinterpret_cast<uintptr_t>(d_err_log),
-      reinterpret_cast<uintptr_t>(d_out), ostride, o.waves8, o.force_packed);
+hipError_t launch_reconstruct(const CodeParams &p, const DevTables &t, const ReconCall &c, void *scratch,
+                              hipStream_t s) {
+  const Kernel kern = choose_reconstruct(p, c, recon_overrides());
   switch (kern) {
-    case Kernel::reconstruct_n1024x:
-      return launch_reconstruct_n1024x(p, t, d_shards, slen, sstride, d_present, d_err_log, d_pattern,
-                                       batch, d_out, ostride, scratch, s);
+    case Kernel::reconstruct_n1024x: return launch_reconstruct_n1024x(p, t, c, scratch, s);
     case Kernel::reconstruct_n1024:
     case Kernel::reconstruct_n1024_packed:
-      return launch_reconstruct_n1024(p, t, kern == Kernel::reconstruct_n1024_packed, d_shards, slen,
-                                      sstride, d_present, d_err_log, d_pattern, batch, d_out, ostride,
-                                      scratch, s);
-    case Kernel::reconstruct_n4096:
-      return launch_reconstruct_n4096(p, t, d_shards, slen, sstride, d_present, d_err_log, d_pattern,
-                                      batch, d_out, ostride, scratch, s);
-    case Kernel::reconstruct_gen:
-      return launch_reconstruct_gen(p, t, d_shards, slen, sstride, d_present, d_err_log, d_pattern,
-                                    batch, d_out, ostride, scratch, s);
+      return launch_reconstruct_n1024(p, t, kern == Kernel::reconstruct_n1024_packed, c, scratch, s);
+    case Kernel::reconstruct_n4096: return launch_reconstruct_n4096(p, t, c, scratch, s);
+    case Kernel::reconstruct_gen: return launch_reconstruct_gen(p, t, c, scratch, s);
     case Kernel::reconstruct_g: break;
     default:  // an empty call, or the packed form past its 2^32 flattened columns
-      return batch == 0 || slen < 2 ? hipSuccess : hipErrorInvalidValue;
+      return c.batch == 0 || c.slen < 2 ? hipSuccess : hipErrorInvalidValue;
   }
-  const int G = groups_for(p.n);
-  const size_t tiles = (slen / 2 + 4 * G - 1) / (4 * G);
-  const bool lds = p.n <= uint32_t(kLdsSlots);
-  const size_t shm = lds ? 2 * size_t(p.n) * G * sizeof(uint2) : 0;
-  dim3 grid((unsigned)tiles, (unsigned)grid_y(batch));
-  hipLaunchKernelGGL(reconstruct_g, grid, dim3(kBlock), shm, s, d_shards, uint64_t(slen),
-                     uint64_t(sstride), d_present, d_err_log, d_out, uint64_t(ostride), int(p.nv),
-                     ilog2(p.n), ilog2(p.k), ilog2(uint32_t(G)), uint32_t(batch), d_pattern, t,
-                     lds ? nullptr : static_cast<uint2 *>(scratch));
+  const GenericGeo g = generic_geo(p.n, c.slen / 2);
+  dim3 grid((unsigned)g.tiles, (unsigned)grid_y(c.batch));
+  hipLaunchKernelGGL(reconstruct_g, grid, dim3(kBlock), g.shm, s, c.shards, uint64_t(c.slen),
+                     uint64_t(c.sstride), c.present, c.err_log, c.out, uint64_t(c.ostride), int(p.nv),
+                     ilog2(p.n), ilog2(p.k), ilog2(uint32_t(g.G)), uint32_t(c.batch), c.pattern, t,
+                     g.lds ? nullptr : static_cast<uint2 *>(scratch));
   return hipGetLastError();
 }
 
@@ -792,34 +788,28 @@ hipError_t launch_reconstruct(const CodeParams &p, const DevTables &t, const uin
 // per-call launch small enough for ONE systematic_g workgroup keeps it: that
 // workgroup stores the completion signal itself (HostSig), which a separate
 // signal kernel after systematic_w would not match in latency.
-Kernel choose_systematic(const CodeParams &p, size_t slen, size_t sstride, size_t batch, uintptr_t shards,
-                         uintptr_t out, size_t ostride, bool host_signal) {
-  if (batch == 0 || slen < 2) return Kernel::invalid;
-  if (host_signal && batch == 1 && slen / 2 * p.k <= size_t(kBlock)) return Kernel::systematic_g;
-  const bool aligned = shards % 16 == 0 && sstride % 16 == 0 && out % 16 == 0 && (batch == 1 || ostride % 16 == 0);
+Kernel choose_systematic(const CodeParams &p, const SysCall &c, bool host_signal) {
+  if (c.batch == 0 || c.slen < 2) return Kernel::invalid;
+  if (host_signal && c.batch == 1 && c.slen / 2 * p.k <= size_t(kBlock)) return Kernel::systematic_g;
+  const bool aligned = addr(c.shards) % 16 == 0 && c.sstride % 16 == 0 && addr(c.out) % 16 == 0 &&
+                       (c.batch == 1 || c.ostride % 16 == 0);
   return p.k >= 16 && aligned ? Kernel::systematic_w : Kernel::systematic_g;
 }
 
-size_t systematic_scratch_bytes(const CodeParams &p) { return p.k >= 16 ? 256 : 0; }
+size_t systematic_scratch_bytes(const CodeParams &p) { return p.k >= 16 ? kTileCounterBytes : 0; }
 
-hipError_t launch_systematic(const CodeParams &p, const uint8_t *d_shards, size_t slen,
-                             size_t sstride, size_t batch, uint8_t *d_out, size_t ostride,
-                             void *scratch, hipStream_t s, HostSig *sig) {
-  switch (choose_systematic(p, slen, sstride, batch, reinterpret_cast<uintptr_t>(d_shards),
-                            reinterpret_cast<uintptr_t>(d_out), ostride, sig && sig->flag)) {
-    case Kernel::systematic_w:
-      return launch_systematic_w(p, d_shards, slen, sstride, batch, d_out, ostride, scratch, s);
+hipError_t launch_systematic(const CodeParams &p, const SysCall &c, void *scratch, hipStream_t s, HostSig *sig) {
+  switch (choose_systematic(p, c, sig && sig->flag)) {
+    case Kernel::systematic_w: return launch_systematic_w(p, c, scratch, s);
     case Kernel::systematic_g: break;
     default: return hipSuccess;  // an empty call
   }
-  const size_t total = slen / 2 * p.k;
-  size_t blocks = (total + kBlock - 1) / kBlock;
-  if (blocks > 4096) blocks = 4096;
-  const bool fuse = sig && sig->flag && blocks * grid_y(batch) == 1;
+  const unsigned blocks = systematic_g_blocks(p, c.slen);
+  const bool fuse = sig && sig->flag && blocks * grid_y(c.batch) == 1;
   if (fuse) sig->fused = true;
-  hipLaunchKernelGGL(systematic_g, dim3(unsigned(blocks), unsigned(grid_y(batch))), dim3(kBlock), 0,
-                     s, d_shards, uint64_t(slen), uint64_t(sstride), int(p.nv), ilog2(p.k), d_out,
-                     uint64_t(ostride), uint32_t(batch), fuse ? sig->flag : nullptr, fuse ? sig->v : 0u);
+  hipLaunchKernelGGL(systematic_g, dim3(blocks, unsigned(grid_y(c.batch))), dim3(kBlock), 0, s, c.shards,
+                     uint64_t(c.slen), uint64_t(c.sstride), int(p.nv), ilog2(p.k), c.out, uint64_t(c.ostride),
+                     uint32_t(c.batch), fuse ? sig->flag : nullptr, fuse ? sig->v : 0u);
   return hipGetLastError();
 }
 
@@ -836,18 +826,6 @@ uint32_t ragged_reconstruct_tile(const CodeParams &p) {
                                                                                  : 4u * uint32_t(groups_for(p.n));
 }
 
-size_t ragged_encode_g_scratch_bytes(const CodeParams &p, size_t batch, size_t max_plen) {
-  if (p.k <= uint32_t(kLdsSlots)) return 0;
-  const size_t tiles = (shard_len(p.k, max_plen) / 2 + 3) / 4;
-  return tiles * grid_y(batch) * 2 * size_t(p.k) * sizeof(uint2);
-}
-
-size_t ragged_reconstruct_g_scratch_bytes(const CodeParams &p, size_t batch, size_t max_slen) {
-  if (p.n <= uint32_t(kLdsSlots)) return 0;
-  const size_t tiles = (max_slen / 2 + 3) / 4;
-  return tiles * grid_y(batch) * 2 * size_t(p.n) * sizeof(uint2);
-}
-
 // columns per plan tile of the systematic ragged kernels: systematic_w's
 // tile; below k = 16 (systematic_g_ragged only asks whether an item has tiles)
 // the 4096 columns of one sweep of its grid
@@ -855,42 +833,34 @@ uint32_t ragged_systematic_tile(const CodeParams &p) {
   return choose_systematic_ragged(p) == RaggedKernel::systematic_w_ragged ? systematic_w_cols(p) : 4096u;
 }
 
-hipError_t launch_systematic_g_ragged(const CodeParams &p, const uint8_t *d_shards, const RaggedItem *d_items,
-                                      size_t batch, size_t max_slen, uint8_t *d_out, void *ws, hipStream_t s) {
-  const size_t total = max_slen / 2 * p.k;
-  size_t blocks = (total + kBlock - 1) / kBlock;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(systematic_g_ragged, dim3(unsigned(blocks), unsigned(grid_y(batch))), dim3(kBlock), 0, s,
-                     d_shards, d_items, ragged_first(ws), ilog2(p.k), d_out, uint32_t(batch));
+hipError_t launch_systematic_g_ragged(const CodeParams &p, const RaggedCall &c, void *ws, hipStream_t s) {
+  hipLaunchKernelGGL(systematic_g_ragged, dim3(systematic_g_blocks(p, c.max_len), unsigned(grid_y(c.batch))),
+                     dim3(kBlock), 0, s, c.in, c.items, ragged_first(ws), ilog2(p.k), c.out, uint32_t(c.batch));
   return hipGetLastError();
 }
 
-hipError_t launch_encode_g_ragged(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,
-                                  const RaggedItem *d_items, size_t batch, size_t max_plen, uint8_t *d_shards,
-                                  void *ws, hipStream_t s) {
-  const int G = groups_for(p.k);
-  const size_t tiles = (shard_len(p.k, max_plen) / 2 + 4 * G - 1) / (4 * G);
-  const bool lds = p.k <= uint32_t(kLdsSlots);
-  const size_t shm = lds ? 2 * size_t(p.k) * G * sizeof(uint2) : 0;
-  uint2 *scratch = reinterpret_cast<uint2 *>(static_cast<uint8_t *>(ws) + ragged_scratch_offset(batch));
-  hipLaunchKernelGGL(encode_g_ragged, dim3(unsigned(tiles), unsigned(grid_y(batch))), dim3(kBlock), shm, s,
-                     d_payloads, d_items, ragged_first(ws), d_shards, int(p.nv), ilog2(p.n), ilog2(p.k),
-                     ilog2(uint32_t(G)), uint32_t(batch), t, lds ? nullptr : scratch);
+namespace {
+uint2 *ragged_g_scratch(const GenericGeo &g, size_t batch, void *ws) {
+  return g.lds ? nullptr : reinterpret_cast<uint2 *>(static_cast<uint8_t *>(ws) + ragged_scratch_offset(batch));
+}
+}  // namespace
+
+hipError_t launch_encode_g_ragged(const CodeParams &p, const DevTables &t, const RaggedCall &c, void *ws,
+                                  hipStream_t s) {
+  const GenericGeo g = generic_geo(p.k, shard_len(p.k, c.max_len) / 2);
+  hipLaunchKernelGGL(encode_g_ragged, dim3(unsigned(g.tiles), unsigned(grid_y(c.batch))), dim3(kBlock), g.shm, s,
+                     c.in, c.items, ragged_first(ws), c.out, int(p.nv), ilog2(p.n), ilog2(p.k),
+                     ilog2(uint32_t(g.G)), uint32_t(c.batch), t, ragged_g_scratch(g, c.batch, ws));
   return hipGetLastError();
 }
 
-hipError_t launch_reconstruct_g_ragged(const CodeParams &p, const DevTables &t, const uint8_t *d_shards,
-                                       const RaggedItem *d_items, const uint8_t *d_present,
-                                       const uint16_t *d_err_log, const uint32_t *d_pattern, size_t batch,
-                                       size_t max_slen, uint8_t *d_out, void *ws, hipStream_t s) {
-  const int G = groups_for(p.n);
-  const size_t tiles = (max_slen / 2 + 4 * G - 1) / (4 * G);
-  const bool lds = p.n <= uint32_t(kLdsSlots);
-  const size_t shm = lds ? 2 * size_t(p.n) * G * sizeof(uint2) : 0;
-  uint2 *scratch = reinterpret_cast<uint2 *>(static_cast<uint8_t *>(ws) + ragged_scratch_offset(batch));
-  hipLaunchKernelGGL(reconstruct_g_ragged, dim3(unsigned(tiles), unsigned(grid_y(batch))), dim3(kBlock), shm, s,
-                     d_shards, d_items, ragged_first(ws), d_present, d_err_log, d_out, int(p.nv), ilog2(p.n),
-                     ilog2(p.k), ilog2(uint32_t(G)), uint32_t(batch), d_pattern, t, lds ? nullptr : scratch);
+hipError_t launch_reconstruct_g_ragged(const CodeParams &p, const DevTables &t, const RaggedCall &c, void *ws,
+                                       hipStream_t s) {
+  const GenericGeo g = generic_geo(p.n, c.max_len / 2);
+  hipLaunchKernelGGL(reconstruct_g_ragged, dim3(unsigned(g.tiles), unsigned(grid_y(c.batch))), dim3(kBlock), g.shm, s,
+                     c.in, c.items, ragged_first(ws), c.present, c.err_log, c.out, int(p.nv), ilog2(p.n),
+                     ilog2(p.k), ilog2(uint32_t(g.G)), uint32_t(c.batch), c.pattern, t,
+                     ragged_g_scratch(g, c.batch, ws));
   return hipGetLastError();
 }
 

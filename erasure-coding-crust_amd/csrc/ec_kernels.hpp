@@ -97,11 +97,52 @@ struct HostSig {
 // failed call is retried on the next launch (ec_runtime.cpp).
 hipError_t prepare_kernel(const void *fn, int lds_bytes, int *cus);
 
-// Scratch (global memory) needed by each launch for FFT sizes whose working
-// set does not fit LDS; 0 for the common sizes.
+// One batch call's buffers, lengths and pitches: built once where the call
+// enters the library and handed down by const reference to the chooser, the
+// launcher and the kernel's own launcher.  Plain data; device or (per-call
+// paths) pinned host pointers.
+struct EncodeCall {
+  const uint8_t *payloads;
+  size_t plen, pstride, batch;
+  uint8_t *shards;
+  size_t sstride;
+};
+// pattern (nullable): payload b's erasure pattern is row pattern[b] of
+// present / err_log (NULL: row b)
+struct ReconCall {
+  const uint8_t *shards;
+  size_t slen, sstride;
+  const uint8_t *present;
+  const uint16_t *err_log;
+  const uint32_t *pattern;
+  size_t batch;
+  uint8_t *out;
+  size_t ostride;
+};
+struct SysCall {
+  const uint8_t *shards;
+  size_t slen, sstride, batch;
+  uint8_t *out;
+  size_t ostride;
+};
+// a pointer as the choosers look at it: an address, never dereferenced
+inline uintptr_t addr(const void *p) { return reinterpret_cast<uintptr_t>(p); }
+
+// A dynamic schedule's tile counter: one word on a 256-B block of its own.  The
+// whole scratch of the k = 16 .. 1024 fast encodes and of systematic_w
+// (optional: a kernel without it runs the static schedule), and the last
+// block of the n = 1024 reconstructs' scratch.
+constexpr size_t kTileCounterBytes = 256;
+
+// Scratch (global memory) needed by each launch: the tile counter, the
+// reconstructs' gather orders, and the generic kernels' transform buffers for
+// FFT sizes whose working set does not fit LDS (generic_scratch_bytes: a
+// transform of `size` points over `positions` pieces / shard positions per
+// payload; 0 for the common sizes).
 size_t encode_scratch_bytes(const CodeParams &p, size_t payload_len, size_t batch);
 bool encode_scratch_optional(const CodeParams &p);  // only a tile counter: static schedule without it
 size_t reconstruct_scratch_bytes(const CodeParams &p, size_t shard_len, size_t batch);
+size_t generic_scratch_bytes(uint32_t size, size_t positions, size_t batch);
 
 // The kernel a batch call runs: decided by the code, the lengths, the batch
 // and the alignment of every base and pitch, in choose_encode /
@@ -133,19 +174,15 @@ const char *kernel_name(Kernel k);  // the enumerator's name; nullptr for invali
 // reconstruct_n1024x in its 12-wave form at every size, n1024x_waves) and
 // ECCR_AMD_RECON_PACKED=1 (force_packed: reconstruct_n1024 packed at every
 // size), read from the environment once per process.
-Kernel choose_encode(const CodeParams &p, size_t payload_len, size_t payload_stride, size_t batch,
-                     uintptr_t payloads, uintptr_t shards, size_t shard_stride);
+Kernel choose_encode(const CodeParams &p, const EncodeCall &c);
 struct ReconOverrides {
   bool waves8 = false, waves12 = false, force_packed = false;
 };
 const ReconOverrides &recon_overrides();
-Kernel choose_reconstruct(const CodeParams &p, size_t shard_len, size_t shard_stride, size_t batch,
-                          uintptr_t shards, uintptr_t present, uintptr_t err_log, uintptr_t out,
-                          size_t out_stride, bool waves8, bool force_packed);
+Kernel choose_reconstruct(const CodeParams &p, const ReconCall &c, const ReconOverrides &o);
 
-hipError_t launch_encode(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,
-                         size_t payload_len, size_t payload_stride, size_t batch, uint8_t *d_shards,
-                         size_t shard_stride, void *scratch, hipStream_t s, HostSig *sig = nullptr);
+hipError_t launch_encode(const CodeParams &p, const DevTables &t, const EncodeCall &c, void *scratch,
+                         hipStream_t s, HostSig *sig = nullptr);
 
 // Erasure locators (poly_encoder.hpp:90-116, folded form), one workgroup per
 // row of d_present.  d_pattern (nullable): rows b with d_pattern[b] != b are
@@ -171,33 +208,25 @@ hipError_t launch_dedup_patterns(const CodeParams &p, const uint8_t *d_present, 
 hipError_t launch_broadcast_locators(const CodeParams &p, const uint32_t *d_pattern, size_t batch,
                                      uint16_t *d_err_log, hipStream_t s);
 
-// d_pattern (nullable): payload b's erasure pattern is row d_pattern[b] of
-// d_present / d_err_log (NULL: row b)
-hipError_t launch_reconstruct(const CodeParams &p, const DevTables &t, const uint8_t *d_shards,
-                              size_t shard_len, size_t shard_stride, const uint8_t *d_present,
-                              const uint16_t *d_err_log, const uint32_t *d_pattern, size_t batch,
-                              uint8_t *d_out, size_t out_stride, void *scratch, hipStream_t s);
+hipError_t launch_reconstruct(const CodeParams &p, const DevTables &t, const ReconCall &c, void *scratch,
+                              hipStream_t s);
 
 // The systematic recovery's kernel (a pure host function, like the two above):
 // systematic_w (sys_w.hip) for k >= 16 with the shard base and pitch, the out
 // base and (batch > 1) the out pitch on 16 B; systematic_g otherwise, and for
 // a per-call launch whose single workgroup stores the completion signal itself
 // (host_signal: the caller passes a HostSig).
-Kernel choose_systematic(const CodeParams &p, size_t shard_len, size_t shard_stride, size_t batch,
-                         uintptr_t shards, uintptr_t out, size_t out_stride, bool host_signal);
+Kernel choose_systematic(const CodeParams &p, const SysCall &c, bool host_signal);
 // scratch (nullable: static tile schedule): systematic_w's tile counter,
-// systematic_scratch_bytes
+// systematic_scratch_bytes (kTileCounterBytes from k = 16 on)
 size_t systematic_scratch_bytes(const CodeParams &p);
-hipError_t launch_systematic(const CodeParams &p, const uint8_t *d_shards, size_t shard_len,
-                             size_t shard_stride, size_t batch, uint8_t *d_out, size_t out_stride,
-                             void *scratch, hipStream_t s, HostSig *sig = nullptr);
+hipError_t launch_systematic(const CodeParams &p, const SysCall &c, void *scratch, hipStream_t s,
+                             HostSig *sig = nullptr);
 // systematic_w's tile: columns per tile (16384 / min(k, 256)) and the row
 // blocks a column tile is walked in (k / 256 above k = 256)
 uint32_t systematic_w_cols(const CodeParams &p);
 uint32_t systematic_w_row_blocks(const CodeParams &p);
-hipError_t launch_systematic_w(const CodeParams &p, const uint8_t *d_shards, size_t shard_len,
-                               size_t shard_stride, size_t batch, uint8_t *d_out, size_t out_stride,
-                               void *scratch, hipStream_t s);
+hipError_t launch_systematic_w(const CodeParams &p, const SysCall &c, void *scratch, hipStream_t s);
 
 // the per-call encode of tiny codes (enc_tiny.hip): n <= kTinyMaxN, payload
 // <= kTinyBytes and the code's tables carried in the kernel arguments, one workgroup, output rows
@@ -229,44 +258,34 @@ bool k256_applicable(const CodeParams &p);
 constexpr size_t kK256Tile = 128, kN1024Cols = 32, kN1024xMinCols = 48, kN1024x16MinCols = 145;
 // encode_k256_packed (choose_encode): the packed (flattened-piece,
 // any-alignment) kernel for small payloads or pitches the unpacked kernels
-// cannot take; no scratch
-hipError_t launch_encode_k256(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,
-                              size_t plen, size_t pstride, size_t batch, uint8_t *d_shards,
-                              size_t sstride, hipStream_t s);
+// cannot take; no scratch (the argument is not looked at)
+hipError_t launch_encode_k256(const CodeParams &p, const DevTables &t, const EncodeCall &c, void *scratch,
+                              hipStream_t s);
 // encode_k256w (n = 1024, unpacked): two 8-wave workgroups per
-// CU on the compact image, tiles scheduled dynamically from a counter in
-// `scratch` (enc_k256w.hip); k256_scratch_bytes: that counter, and the one of
-// encode_kw<8> at n = 2048 (nullable: static tile schedule)
-size_t k256_scratch_bytes(const CodeParams &p);
-hipError_t launch_encode_k256w(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,
-                               size_t plen, size_t pstride, size_t batch, uint8_t *d_shards,
-                               size_t sstride, void *scratch, hipStream_t s);
+// CU on the compact image, tiles scheduled dynamically from the tile counter
+// in `scratch` (enc_k256w.hip; nullable: static tile schedule)
+hipError_t launch_encode_k256w(const CodeParams &p, const DevTables &t, const EncodeCall &c, void *scratch,
+                               hipStream_t s);
 
-// specialised kernels (enc_k1024.hip): k = 1024, n = 4096, needs a coefficient
-// scratch of k1024_scratch_bytes
+// specialised kernels (enc_k1024.hip): k = 1024, n = 4096; scratch (nullable)
+// the tile counter
 bool k1024_applicable(const CodeParams &p);
-size_t k1024_scratch_bytes(size_t plen, size_t batch);
-hipError_t launch_encode_k1024(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,
-                               size_t plen, size_t pstride, size_t batch, uint8_t *d_shards,
-                               size_t sstride, void *scratch, hipStream_t s);
+hipError_t launch_encode_k1024(const CodeParams &p, const DevTables &t, const EncodeCall &c, void *scratch,
+                               hipStream_t s);
 
 // k = 512, n = 2048 / 4096 (enc_k512w.hip): two 8-wave workgroups per CU on
 // the compact image and the per-coset extension images; scratch (nullable:
-// static tile schedule) the tile counter, k512w_scratch_bytes
+// static tile schedule) the tile counter
 bool k512w_applicable(const CodeParams &p);
-size_t k512w_scratch_bytes(const CodeParams &p);
-hipError_t launch_encode_k512w(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,
-                               size_t plen, size_t pstride, size_t batch, uint8_t *d_shards,
-                               size_t sstride, void *scratch, hipStream_t s);
+hipError_t launch_encode_k512w(const CodeParams &p, const DevTables &t, const EncodeCall &c, void *scratch,
+                               hipStream_t s);
 
 // k = 16 .. 128, n <= 8 k, and k = 256 at n = 2048 (enc_kw.hip): the same
 // model on the compact image (+ coset extension tables at k = 256); scratch
-// (nullable) the tile counter, kw_scratch_bytes
+// (nullable) the tile counter
 bool kw_applicable(const CodeParams &p);
-size_t kw_scratch_bytes(const CodeParams &p);
-hipError_t launch_encode_kw(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,
-                            size_t plen, size_t pstride, size_t batch, uint8_t *d_shards,
-                            size_t sstride, void *scratch, hipStream_t s);
+hipError_t launch_encode_kw(const CodeParams &p, const DevTables &t, const EncodeCall &c, void *scratch,
+                            hipStream_t s);
 
 // Per-payload gather order of the received rows, present rows first, per
 // 1024-row quarter (or the n < 1024 rows; dec_n1024.hip): the scratch of
@@ -279,39 +298,28 @@ hipError_t launch_gather_order(const CodeParams &p, const uint8_t *d_present,
 // specialised kernels (dec_n1024.hip); scratch: n1024_scratch_bytes(p, batch)
 bool n1024_applicable(const CodeParams &p);
 // packed (choose_reconstruct): flattened columns, any even shard pitch and base
-hipError_t launch_reconstruct_n1024(const CodeParams &p, const DevTables &t, bool packed,
-                                    const uint8_t *d_shards, size_t slen, size_t sstride,
-                                    const uint8_t *d_present, const uint16_t *d_err_log,
-                                    const uint32_t *d_pattern, size_t batch, uint8_t *d_out,
-                                    size_t ostride, void *scratch, hipStream_t s);
+hipError_t launch_reconstruct_n1024(const CodeParams &p, const DevTables &t, bool packed, const ReconCall &c,
+                                    void *scratch, hipStream_t s);
 // reconstruct_n1024x (dec_n1024x.hip) for the unpacked case, in its 12- or
 // 16-wave form: n1024x_waves(shard_len), a pure host function.  Every n = 1024
-// form takes n1024_scratch_bytes (the gather order + n1024x's tile counter)
+// form takes n1024_scratch_bytes (the gather order + n1024x's tile counter,
+// kTileCounterBytes)
 int n1024x_waves(size_t slen);
 size_t n1024_scratch_bytes(const CodeParams &p, size_t batch);
 size_t n1024_tick_offset(const CodeParams &p, size_t batch);
-hipError_t launch_reconstruct_n1024x(const CodeParams &p, const DevTables &t,
-                                     const uint8_t *d_shards, size_t slen, size_t sstride,
-                                     const uint8_t *d_present, const uint16_t *d_err_log,
-                                     const uint32_t *d_pattern, size_t batch, uint8_t *d_out,
-                                     size_t ostride, void *scratch, hipStream_t s);
+hipError_t launch_reconstruct_n1024x(const CodeParams &p, const DevTables &t, const ReconCall &c, void *scratch,
+                                     hipStream_t s);
 
 // specialised kernels (dec_n4096.hip); scratch: n4096_scratch_bytes(p, batch)
 bool n4096_applicable(const CodeParams &p);
 size_t n4096_scratch_bytes(const CodeParams &p, size_t batch);
-hipError_t launch_reconstruct_n4096(const CodeParams &p, const DevTables &t,
-                                    const uint8_t *d_shards, size_t slen, size_t sstride,
-                                    const uint8_t *d_present, const uint16_t *d_err_log,
-                                    const uint32_t *d_pattern, size_t batch, uint8_t *d_out,
-                                    size_t ostride, void *scratch, hipStream_t s);
+hipError_t launch_reconstruct_n4096(const CodeParams &p, const DevTables &t, const ReconCall &c, void *scratch,
+                                    hipStream_t s);
 
 // register-blocked reconstruct for 64 <= n <= 1024, 16 <= k <= 512 (dec_gen.hip);
 // scratch: gather_order_bytes(p, batch)
 bool decgen_applicable(const CodeParams &p);
-hipError_t launch_reconstruct_gen(const CodeParams &p, const DevTables &t,
-                                  const uint8_t *d_shards, size_t slen, size_t sstride,
-                                  const uint8_t *d_present, const uint16_t *d_err_log,
-                                  const uint32_t *d_pattern, size_t batch, uint8_t *d_out,
-                                  size_t ostride, void *scratch, hipStream_t s);
+hipError_t launch_reconstruct_gen(const CodeParams &p, const DevTables &t, const ReconCall &c, void *scratch,
+                                  hipStream_t s);
 
 }  // namespace ecamd

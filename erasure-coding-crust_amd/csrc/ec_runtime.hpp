@@ -5,10 +5,12 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
 
+#include "../../include/erasure_coding/erasure_coding.h"
 #include "ec_kernels.hpp"
 #include "gf_field.hpp"
 
@@ -173,5 +175,25 @@ bool ensure_dev(void **p, size_t *cap, size_t need);
 
 void set_error(const std::string &msg);  // also printed to stderr
 const char *last_error();
+
+// ---- shared by the C-ABI files (capi.cpp, host_pipeline.hip)
+// false, with the thread's last error set to `what` and HIP's text, unless e is hipSuccess
+inline bool hip_check(hipError_t e, const char *what) {
+  if (e == hipSuccess) return true;
+  set_error(std::string("erasure_coding_crust(amd): ") + what + ": " + hipGetErrorString(e));
+  return false;
+}
+
+inline NPRSResult result(NPRSResult_Tag tag) {
+  NPRSResult r;
+  std::memset(&r, 0, sizeof r);
+  r.tag = tag;
+  return r;
+}
+
+// device row pitch of the per-call paths: 16-B aligned rows for the fast
+// kernels; the host staging buffers use the same pitch, so every host<->device
+// copy is one linear transfer (a 2-D copy of narrow rows costs ~10 us per row)
+inline size_t dev_pitch(size_t sl) { return (sl + 15) / 16 * 16; }
 
 }  // namespace ecamd

@@ -260,26 +260,23 @@ __global__ void __launch_bounds__(THREADS)
 
 bool k1024_applicable(const CodeParams &p) { return p.k == 1024 && p.n == 4096; }
 
-size_t k1024_scratch_bytes(size_t, size_t) { return 256; }  // the tile counter
-
-hipError_t launch_encode_k1024(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,
-                               size_t plen, size_t pstride, size_t batch, uint8_t *d_shards,
-                               size_t sstride, void *scratch, hipStream_t s) {
+hipError_t launch_encode_k1024(const CodeParams &p, const DevTables &t, const EncodeCall &c, void *scratch,
+                               hipStream_t s) {
   int cus = 0;
-  const size_t sl = shard_len(p.k, plen);
-  const size_t tiles = (sl / 2 + TILE - 1) / TILE * batch;
+  const size_t sl = shard_len(p.k, c.plen);
+  const size_t tiles = (sl / 2 + TILE - 1) / TILE * c.batch;
   if (const hipError_t e = prepare_kernel(reinterpret_cast<const void *>(&encode_k1024_fused), LDS_BYTES, &cus);
       e != hipSuccess)
     return e;
   if (tiles >= (size_t(1) << 32) - size_t(2) * cus) return hipErrorInvalidValue;
-  // the tile counter (k1024_scratch_bytes); none: the static schedule
+  // the tile counter (kTileCounterBytes); none: the static schedule
   uint32_t *tick = static_cast<uint32_t *>(scratch);
   if (tick)
     if (const hipError_t e = launch_zero_counters(tick, sizeof(uint32_t), s); e != hipSuccess) return e;
   const unsigned grid = unsigned(std::min(tiles, size_t(cus)));
-  hipLaunchKernelGGL(encode_k1024_fused, dim3(grid), dim3(THREADS), LDS_BYTES, s, d_payloads,
-                     uint64_t(plen), uint64_t(pstride), d_shards, uint64_t(sl), uint64_t(sstride),
-                     int(p.nv), uint32_t(batch), tick, t);
+  hipLaunchKernelGGL(encode_k1024_fused, dim3(grid), dim3(THREADS), LDS_BYTES, s, c.payloads,
+                     uint64_t(c.plen), uint64_t(c.pstride), c.shards, uint64_t(sl), uint64_t(c.sstride),
+                     int(p.nv), uint32_t(c.batch), tick, t);
   return hipGetLastError();
 }
 

@@ -526,22 +526,21 @@ static_assert(size_t(TILE) == kK256Tile, "choose_encode tests this tile");
 
 // PK = 2 at n = 1024 and PK = 1 at n = 2048; choose_encode has checked the
 // even shard base and pitch and the 2^32 bound of the flattened piece space
-hipError_t launch_encode_k256(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,
-                              size_t plen, size_t pstride, size_t batch, uint8_t *d_shards,
-                              size_t sstride, hipStream_t s) {
+hipError_t launch_encode_k256(const CodeParams &p, const DevTables &t, const EncodeCall &c, void *,
+                              hipStream_t s) {
   int cus = 0;
   const void *fn = p.n == 1024 ? reinterpret_cast<const void *>(&encode_k256<1024, 2>)
                                : reinterpret_cast<const void *>(&encode_k256<2048, 1>);
   if (const hipError_t e = prepare_kernel(fn, LDS_BYTES, &cus); e != hipSuccess) return e;
-  const size_t sl = shard_len(p.k, plen);
+  const size_t sl = shard_len(p.k, c.plen);
   const size_t npp8 = (sl / 2 + 7) / 8 * 8;
-  const size_t tiles = p.n == 1024 ? ((sl / 2) * batch + 7) / 8  // wave tasks, spread over the CUs
-                                   : (npp8 * batch + TILE - 1) / TILE;
+  const size_t tiles = p.n == 1024 ? ((sl / 2) * c.batch + 7) / 8  // wave tasks, spread over the CUs
+                                   : (npp8 * c.batch + TILE - 1) / TILE;
   const unsigned grid = unsigned(tiles < size_t(cus) ? tiles : size_t(cus));
-#define ECAMD_K256(NN, PK)                                                                       \
-  hipLaunchKernelGGL((encode_k256<NN, PK>), dim3(grid), dim3(THREADS), LDS_BYTES, s, d_payloads,   \
-                     uint64_t(plen), uint64_t(pstride), d_shards, uint64_t(sl), uint64_t(sstride), \
-                     int(p.nv), uint32_t(batch), uint32_t(npp8), t)
+#define ECAMD_K256(NN, PK)                                                                           \
+  hipLaunchKernelGGL((encode_k256<NN, PK>), dim3(grid), dim3(THREADS), LDS_BYTES, s, c.payloads,       \
+                     uint64_t(c.plen), uint64_t(c.pstride), c.shards, uint64_t(sl), uint64_t(c.sstride), \
+                     int(p.nv), uint32_t(c.batch), uint32_t(npp8), t)
   if (p.n == 1024) ECAMD_K256(1024, 2);
   else ECAMD_K256(2048, 1);
 #undef ECAMD_K256

@@ -34,17 +34,11 @@ __global__ void __launch_bounds__(THREADS, 4) encode_k256w(const uint8_t *__rest
 #include "enc_k256w_tile.inc"
 }
 
-hipError_t launch_encode_k256w(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,
-                               size_t plen, size_t pstride, size_t batch, uint8_t *d_shards,
-                               size_t sstride, void *scratch, hipStream_t s) {
+hipError_t launch_encode_k256w(const CodeParams &p, const DevTables &t, const EncodeCall &c, void *scratch,
+                               hipStream_t s) {
   if (!t.cimg) return hipErrorInvalidValue;
   if (p.nv <= 2 * k256w::K || p.nv > 1024) return hipErrorInvalidValue;  // cosets 256, 512 (, 768)
-  return launch_w(encode_k256w, k256w::lds_bytes<k256w::UniformGeo>(), k256w::TILE, p, d_payloads, plen, pstride,
-                  batch, d_shards, sstride, scratch, s, t.cimg);
+  return launch_w(encode_k256w, k256w::lds_bytes<k256w::UniformGeo>(), k256w::TILE, p, c, scratch, s, t.cimg);
 }
-
-// the tile counter of the two unpacked k = 256 kernels, encode_k256w (here)
-// and encode_kw<8> (n = 2048, enc_kw.hip): one word on a line of its own
-size_t k256_scratch_bytes(const CodeParams &) { return 256; }
 
 }  // namespace ecamd

@@ -132,8 +132,8 @@ __global__ void __launch_bounds__(THREADS, 4) encode_k256w_ragged(const RaggedHd
 // The grid is sized from the most tiles the call can have (the host does not
 // know the items): workgroups beyond the real count take a ticket past the end
 // and leave.
-hipError_t launch_encode_k256w_ragged(const CodeParams &p, const DevTables &t, size_t batch, size_t max_plen,
-                                      void *ws, hipStream_t s) {
+hipError_t launch_encode_k256w_ragged(const CodeParams &p, const DevTables &t, const RaggedCall &c, void *ws,
+                                      hipStream_t s) {
   if (!t.cimg || !ws) return hipErrorInvalidValue;
   if (p.nv <= 2 * k256w::K || p.nv > 1024) return hipErrorInvalidValue;  // cosets 256, 512 (, 768)
   constexpr int kLds = k256w::lds_bytes<k256w::RaggedGeo>();
@@ -141,7 +141,7 @@ hipError_t launch_encode_k256w_ragged(const CodeParams &p, const DevTables &t, s
   if (const hipError_t e = prepare_kernel(reinterpret_cast<const void *>(&encode_k256w_ragged), kLds, &cus);
       e != hipSuccess)
     return e;
-  const size_t most = (shard_len(p.k, max_plen) / 2 + k256w::TILE - 1) / k256w::TILE * batch;
+  const size_t most = (shard_len(p.k, c.max_len) / 2 + k256w::TILE - 1) / k256w::TILE * c.batch;
   if (most + 4096 >= (size_t(1) << 32)) return hipErrorInvalidValue;  // 32-bit tile tickets
   const size_t slots = 2 * size_t(cus);
   hipLaunchKernelGGL(encode_k256w_ragged, dim3(unsigned(most < slots ? most : slots)), dim3(THREADS), kLds, s,

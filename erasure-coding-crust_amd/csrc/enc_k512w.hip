@@ -419,15 +419,11 @@ __global__ void __launch_bounds__(THREADS, 4) encode_k512w(const uint8_t *__rest
 
 bool k512w_applicable(const CodeParams &p) { return p.k == 512 && (p.n == 2048 || p.n == 4096); }
 
-size_t k512w_scratch_bytes(const CodeParams &p) { return k512w_applicable(p) ? 256 : 0; }
-
-hipError_t launch_encode_k512w(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,
-                               size_t plen, size_t pstride, size_t batch, uint8_t *d_shards,
-                               size_t sstride, void *scratch, hipStream_t s) {
+hipError_t launch_encode_k512w(const CodeParams &p, const DevTables &t, const EncodeCall &c, void *scratch,
+                               hipStream_t s) {
   if (!t.cimg || !t.eimg512) return hipErrorInvalidValue;
   if (!k512w_applicable(p) || p.nv <= uint32_t(K) || p.nv > p.n) return hipErrorInvalidValue;
-  return launch_w(encode_k512w, LDS_BYTES, TILE, p, d_payloads, plen, pstride, batch, d_shards, sstride, scratch,
-                  s, t.cimg, t.eimg512);
+  return launch_w(encode_k512w, LDS_BYTES, TILE, p, c, scratch, s, t.cimg, t.eimg512);
 }
 
 }  // namespace ecamd

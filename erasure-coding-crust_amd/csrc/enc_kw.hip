@@ -409,27 +409,22 @@ bool kw_applicable(const CodeParams &p) {
          (p.k == 256 && p.n == 2048);
 }
 
-size_t kw_scratch_bytes(const CodeParams &p) { return kw_applicable(p) ? 256 : 0; }
-
 template <int M>
-static hipError_t launch_m(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads, size_t plen,
-                           size_t pstride, size_t batch, uint8_t *d_shards, size_t sstride, void *scratch,
+static hipError_t launch_m(const CodeParams &p, const DevTables &t, const EncodeCall &c, void *scratch,
                            hipStream_t s) {
-  return launch_w(encode_kw<M>, lds_bytes<M>(), Geo<M>::TILE, p, d_payloads, plen, pstride, batch, d_shards,
-                  sstride, scratch, s, t.cimg, t.eimg256);
+  return launch_w(encode_kw<M>, lds_bytes<M>(), Geo<M>::TILE, p, c, scratch, s, t.cimg, t.eimg256);
 }
 
-hipError_t launch_encode_kw(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,
-                            size_t plen, size_t pstride, size_t batch, uint8_t *d_shards,
-                            size_t sstride, void *scratch, hipStream_t s) {
+hipError_t launch_encode_kw(const CodeParams &p, const DevTables &t, const EncodeCall &c, void *scratch,
+                            hipStream_t s) {
   if (!t.cimg || !kw_applicable(p) || p.nv <= p.k || p.nv > p.n) return hipErrorInvalidValue;
   if (p.k == 256 && (!t.eimg256 || p.nv <= 4 * p.k)) return hipErrorInvalidValue;  // cosets 4.. exist (n = 2048)
   switch (p.k) {
-    case 16: return launch_m<4>(p, t, d_payloads, plen, pstride, batch, d_shards, sstride, scratch, s);
-    case 32: return launch_m<5>(p, t, d_payloads, plen, pstride, batch, d_shards, sstride, scratch, s);
-    case 64: return launch_m<6>(p, t, d_payloads, plen, pstride, batch, d_shards, sstride, scratch, s);
-    case 128: return launch_m<7>(p, t, d_payloads, plen, pstride, batch, d_shards, sstride, scratch, s);
-    default: return launch_m<8>(p, t, d_payloads, plen, pstride, batch, d_shards, sstride, scratch, s);
+    case 16: return launch_m<4>(p, t, c, scratch, s);
+    case 32: return launch_m<5>(p, t, c, scratch, s);
+    case 64: return launch_m<6>(p, t, c, scratch, s);
+    case 128: return launch_m<7>(p, t, c, scratch, s);
+    default: return launch_m<8>(p, t, c, scratch, s);
   }
 }
 

@@ -317,28 +317,27 @@ __device__ __forceinline__ void store_own(uint8_t *SH, uint64_t sstride, uint32_
 // ---- the launchers' tail: the kernel prepared for its dynamic LDS, the tile
 // count (payload pieces in tiles of `tile`) below 2^32 - 4 CUs (the kernels
 // count tiles, and the static schedule's cur + gridDim.x, in 32 bits), the
-// tile counter (`scratch`: k256_scratch_bytes and its like) zeroed in stream
+// tile counter (`scratch`: kTileCounterBytes) zeroed in stream
 // order, grid = min(tiles, two workgroups per CU).  No scratch: the static
 // schedule (a missing counter costs speed, not an error).  `tabs`: the
 // kernel's table images, passed between batch and the counter.
 template <typename Kern, typename... Tabs>
-hipError_t launch_w(Kern kern, int lds_bytes, size_t tile, const CodeParams &p, const uint8_t *d_payloads,
-                    size_t plen, size_t pstride, size_t batch, uint8_t *d_shards, size_t sstride,
-                    void *scratch, hipStream_t s, Tabs... tabs) {
+hipError_t launch_w(Kern kern, int lds_bytes, size_t tile, const CodeParams &p, const EncodeCall &c, void *scratch,
+                    hipStream_t s, Tabs... tabs) {
   int cus = 0;
   if (const hipError_t e = prepare_kernel(reinterpret_cast<const void *>(kern), lds_bytes, &cus); e != hipSuccess)
     return e;
-  const size_t sl = shard_len(p.k, plen);
-  const size_t tiles = (sl / 2 + tile - 1) / tile * batch;
+  const size_t sl = shard_len(p.k, c.plen);
+  const size_t tiles = (sl / 2 + tile - 1) / tile * c.batch;
   if (tiles >= (size_t(1) << 32) - size_t(4) * cus) return hipErrorInvalidValue;
   uint32_t *tick = static_cast<uint32_t *>(scratch);
   if (tick)
     if (const hipError_t e = launch_zero_counters(tick, sizeof(uint32_t), s); e != hipSuccess) return e;
   const size_t slots = 2 * size_t(cus);
   const unsigned grid = unsigned(tiles < slots ? tiles : slots);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), lds_bytes, s, d_payloads, uint64_t(plen),
-                     uint64_t(pstride), d_shards, uint64_t(sl), uint64_t(sstride), int(p.nv),
-                     uint32_t(batch), tabs..., tick);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(THREADS), lds_bytes, s, c.payloads, uint64_t(c.plen),
+                     uint64_t(c.pstride), c.shards, uint64_t(sl), uint64_t(c.sstride), int(p.nv),
+                     uint32_t(c.batch), tabs..., tick);
   return hipGetLastError();
 }
 

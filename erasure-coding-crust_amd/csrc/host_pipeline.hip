@@ -143,21 +143,6 @@ bool slot_scratch(Slot &s, size_t bytes, void **out) {
   return true;
 }
 
-bool ok(hipError_t e, const char *what) {
-  if (e == hipSuccess) return true;
-  set_error(std::string("erasure_coding_crust(amd): ") + what + ": " + hipGetErrorString(e));
-  return false;
-}
-
-NPRSResult res(NPRSResult_Tag t) {
-  NPRSResult r;
-  std::memset(&r, 0, sizeof r);
-  r.tag = t;
-  return r;
-}
-
-size_t round16(size_t x) { return (x + 15) / 16 * 16; }
-
 uint64_t mix64(uint64_t x) {  // splitmix64 finaliser (pattern hash terms)
   x += 0x9E3779B97F4A7C15ull;
   x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -187,13 +172,13 @@ NPRSResult ECCR_AMD_encode_host_batch(unsigned long nv, const uint8_t *h_payload
                                       unsigned long batch, uint8_t *h_shards,
                                       unsigned long sstride, unsigned long chunk) {
   CodeParams p;
-  if (code_params(nv, &p) != ParamError::kOk) return res(NPRS_RESULT_UNKNOWN_CODE_PARAM);
-  if (plen == 0 || !h_payloads || !h_shards) return res(NPRS_RESULT_BAD_PAYLOAD);
+  if (code_params(nv, &p) != ParamError::kOk) return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
+  if (plen == 0 || !h_payloads || !h_shards) return result(NPRS_RESULT_BAD_PAYLOAD);
   const size_t sl = shard_len(p.k, plen);
-  if (pstride < plen || sstride < sl) return res(NPRS_RESULT_BAD_PAYLOAD);
+  if (pstride < plen || sstride < sl) return result(NPRS_RESULT_BAD_PAYLOAD);
   DeviceState *d = device_state();
   Pipeline *pl = d ? pipeline() : nullptr;
-  if (!pl) return res(NPRS_RESULT_UNKNOWN_CODE_PARAM);
+  if (!pl) return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
   if (chunk == 0) chunk = auto_chunk(plen + size_t(nv) * sl, batch);
   // Device rows use the host stride (one linear copy up) when it already suits
   // the fast kernels or rows are short: a 2-D copy of many narrow rows is
@@ -201,7 +186,7 @@ NPRSResult ECCR_AMD_encode_host_batch(unsigned long nv, const uint8_t *h_payload
   // re-pitched to aligned device strides by a 2-D copy of long rows.
   const bool pay_lin = pstride % 16 == 0 || plen < 256;
   const bool sh_lin = sstride % 8 == 0 || sl < 256;
-  const size_t dps = pay_lin ? pstride : round16(plen);
+  const size_t dps = pay_lin ? pstride : dev_pitch(plen);
   const size_t dss = sh_lin ? sstride : (sl + 63) / 64 * 64;
   // The rows come back in one linear copy only if that writes nothing but the
   // rows: tight rows, or short padded rows whose span was first brought up
@@ -214,33 +199,34 @@ NPRSResult ECCR_AMD_encode_host_batch(unsigned long nv, const uint8_t *h_payload
     Slot &s = pl->slot[i % kSlots];
     const size_t cb = batch - c0 < chunk ? batch - c0 : chunk;
     if (!grow(&s.d_a, &s.cap_a, chunk * dps) || !grow(&s.d_b, &s.cap_b, chunk * nv * dss))
-      return res(NPRS_RESULT_UNKNOWN_CODE_PARAM);
+      return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
     void *scratch = nullptr;
     if (!slot_scratch(s, encode_scratch_bytes(p, plen, cb), &scratch))
-      return res(NPRS_RESULT_UNKNOWN_CODE_PARAM);
+      return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
     const uint8_t *hp = h_payloads + c0 * pstride;
     uint8_t *hs = h_shards + c0 * nv * sstride;
     const hipError_t up =
         pay_lin ? hipMemcpyAsync(s.d_a, hp, (cb - 1) * pstride + plen, hipMemcpyHostToDevice, s.stream)
                 : hipMemcpy2DAsync(s.d_a, dps, hp, pstride, plen, cb, hipMemcpyHostToDevice, s.stream);
-    if (!ok(up, "H2D payloads") ||
-        (sh_pre && !ok(hipMemcpyAsync(s.d_b, hs, (cb * nv - 1) * sstride + sl, hipMemcpyHostToDevice, s.stream),
-                       "H2D shard rows' surroundings")) ||
-        !ok(launch_encode(p, device_tables(d), s.d_a, plen, dps, cb, s.d_b, dss, scratch, s.stream),
-            "encode launch"))
-      return res(NPRS_RESULT_UNKNOWN_CODE_PARAM);
+    const EncodeCall call{s.d_a, plen, dps, cb, s.d_b, dss};
+    if (!hip_check(up, "H2D payloads") ||
+        (sh_pre &&
+         !hip_check(hipMemcpyAsync(s.d_b, hs, (cb * nv - 1) * sstride + sl, hipMemcpyHostToDevice, s.stream),
+                    "H2D shard rows' surroundings")) ||
+        !hip_check(launch_encode(p, device_tables(d), call, scratch, s.stream), "encode launch"))
+      return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
     const hipError_t down =
         sh_down_lin ? hipMemcpyAsync(hs, s.d_b, (cb * nv - 1) * sstride + sl, hipMemcpyDeviceToHost,
                                      s.stream)
                     : hipMemcpy2DAsync(hs, sstride, s.d_b, dss, sl, cb * nv, hipMemcpyDeviceToHost,
                                        s.stream);
-    if (!ok(down, "D2H shards"))
-      return res(NPRS_RESULT_UNKNOWN_CODE_PARAM);
+    if (!hip_check(down, "D2H shards"))
+      return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
   }
   for (Slot &s : pl->slot)
-    if (!ok(hipStreamSynchronize(s.stream), "encode_host_batch"))
-      return res(NPRS_RESULT_UNKNOWN_CODE_PARAM);
-  return res(NPRS_RESULT_OK);
+    if (!hip_check(hipStreamSynchronize(s.stream), "encode_host_batch"))
+      return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
+  return result(NPRS_RESULT_OK);
 }
 
 NPRSResult ECCR_AMD_reconstruct_host_batch(unsigned long nv, const uint8_t *h_shards,
@@ -249,11 +235,11 @@ NPRSResult ECCR_AMD_reconstruct_host_batch(unsigned long nv, const uint8_t *h_sh
                                            unsigned long batch, uint8_t *h_out,
                                            unsigned long ostride, unsigned long chunk) {
   CodeParams p;
-  if (code_params(nv, &p) != ParamError::kOk) return res(NPRS_RESULT_UNKNOWN_CODE_PARAM);
-  if (!h_shards || !h_index || !h_out) return res(NPRS_RESULT_BAD_PAYLOAD);
-  if (slen % 2 != 0) return res(NPRS_RESULT_UNEVEN_LENGTH);
-  if (sstride < slen || ostride < slen * p.k) return res(NPRS_RESULT_NON_UNIFORM_CHUNKS);
-  if (cnt < p.k) return res(NPRS_RESULT_NOT_ENOUGH_CHUNKS);  // reed-solomon.hpp:99-100
+  if (code_params(nv, &p) != ParamError::kOk) return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
+  if (!h_shards || !h_index || !h_out) return result(NPRS_RESULT_BAD_PAYLOAD);
+  if (slen % 2 != 0) return result(NPRS_RESULT_UNEVEN_LENGTH);
+  if (sstride < slen || ostride < slen * p.k) return result(NPRS_RESULT_NON_UNIFORM_CHUNKS);
+  if (cnt < p.k) return result(NPRS_RESULT_NOT_ENOUGH_CHUNKS);  // reed-solomon.hpp:99-100
   // src/erasure_coding.rs:370-375 (index bounds) and reed-solomon.hpp:99-100
   // (enough distinct shards; a repeated index counts once, its rows must agree)
   // per payload: its erasure pattern's hash (sum of mix64 over the distinct
@@ -269,7 +255,7 @@ NPRSResult ECCR_AMD_reconstruct_host_batch(unsigned long nv, const uint8_t *h_sh
     for (unsigned long j = 0; j < cnt; ++j) {
       const uint16_t v = h_index[b * cnt + j];
       if (v >= nv) {
-        NPRSResult r = res(NPRS_RESULT_CHUNK_INDEX_OUT_OF_BOUNDS);
+        NPRSResult r = result(NPRS_RESULT_CHUNK_INDEX_OUT_OF_BOUNDS);
         r.chunk_index_out_of_bounds.chunk_index = v;
         r.chunk_index_out_of_bounds.n_validators = nv;
         return r;
@@ -280,14 +266,14 @@ NPRSResult ECCR_AMD_reconstruct_host_batch(unsigned long nv, const uint8_t *h_sh
         h += term[v];
       }
     }
-    if (distinct < p.k) return res(NPRS_RESULT_NOT_ENOUGH_CHUNKS);
+    if (distinct < p.k) return result(NPRS_RESULT_NOT_ENOUGH_CHUNKS);
     phash[b] = h;
     pcount[b] = uint32_t(distinct);
   }
   DeviceState *d = device_state();
   const uint16_t *fold = d ? device_fold(d, p.n) : nullptr;
   Pipeline *pl = fold ? pipeline() : nullptr;
-  if (!pl) return res(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
+  if (!pl) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
   if (chunk == 0) chunk = auto_chunk(size_t(cnt) * sstride + size_t(slen) * p.k, batch);
   const size_t dss = (slen + 63) / 64 * 64, ob = slen * p.k;
   const bool out_lin = ostride % 8 == 0 || ob < 256;  // as in encode: the host pitch if it suits
@@ -304,15 +290,15 @@ NPRSResult ECCR_AMD_reconstruct_host_batch(unsigned long nv, const uint8_t *h_sh
     if (!grow(&s.d_a, &s.cap_a, chunk * cnt * sstride) || !grow(&s.d_b, &s.cap_b, chunk * nv * dss) ||
         !grow(&s.d_c, &s.cap_c, chunk * dos) || !grow(&s.d_meta, &s.cap_meta, rows_at + chunk * p.n) ||
         !grow(&s.d_elog, &s.cap_elog, chunk * p.n * 2))
-      return res(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
+      return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
     uint32_t *d_pat = reinterpret_cast<uint32_t *>(s.d_meta);
     const uint16_t *d_idx = reinterpret_cast<const uint16_t *>(s.d_meta + pat_bytes);
     uint8_t *d_present = s.d_meta + rows_at;
     // distinct erasure patterns of the chunk: one present
     // row and one locator each; payload b uses row h_pat[b]
-    if (!ok(hipEventSynchronize(s.staged), "staging reuse")) return res(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
+    if (!hip_check(hipEventSynchronize(s.staged), "staging reuse")) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
     if (!ensure_host(&s.h_meta, &s.cap_h_meta, rows_at + chunk * p.n))
-      return res(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
+      return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
     std::memcpy(s.h_meta + pat_bytes, h_index + c0 * cnt, cb * cnt * 2);
     uint32_t *h_pat = reinterpret_cast<uint32_t *>(s.h_meta);
     s.h_rows.clear();
@@ -356,42 +342,40 @@ NPRSResult ECCR_AMD_reconstruct_host_batch(unsigned long nv, const uint8_t *h_sh
     std::memcpy(s.h_meta + rows_at, s.h_rows.data(), size_t(npat) * p.n);
     void *scratch = nullptr;
     if (!slot_scratch(s, reconstruct_scratch_bytes(p, slen, cb), &scratch))
-      return res(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
+      return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
+    const ReconCall call{s.d_b, slen, dss, d_present, s.d_elog, d_pat, cb, s.d_c, dos};
     bool good =
-        ok(hipMemcpyAsync(s.d_a, h_shards + c0 * cnt * sstride, cb * cnt * sstride,
-                          hipMemcpyHostToDevice, s.stream),
-           "H2D shards") &&
-        ok(hipMemcpyAsync(s.d_meta, s.h_meta, rows_at + size_t(npat) * p.n, hipMemcpyHostToDevice,
-                          s.stream),
-           "H2D patterns") &&
-        ok(hipEventRecord(s.staged, s.stream), "staging event") &&
-        (!out_pre || ok(hipMemcpyAsync(s.d_c, h_out + c0 * ostride, (cb - 1) * ostride + ob,
-                                       hipMemcpyHostToDevice, s.stream),
-                        "H2D out rows' surroundings"));
+        hip_check(hipMemcpyAsync(s.d_a, h_shards + c0 * cnt * sstride, cb * cnt * sstride,
+                                 hipMemcpyHostToDevice, s.stream),
+                  "H2D shards") &&
+        hip_check(hipMemcpyAsync(s.d_meta, s.h_meta, rows_at + size_t(npat) * p.n, hipMemcpyHostToDevice,
+                                 s.stream),
+                  "H2D patterns") &&
+        hip_check(hipEventRecord(s.staged, s.stream), "staging event") &&
+        (!out_pre || hip_check(hipMemcpyAsync(s.d_c, h_out + c0 * ostride, (cb - 1) * ostride + ob,
+                                              hipMemcpyHostToDevice, s.stream),
+                               "H2D out rows' surroundings"));
     if (good) {
       hipLaunchKernelGGL(scatter_present, dim3(unsigned(cnt), unsigned(cb < 65535 ? cb : 65535)), dim3(256),
                          0, s.stream, s.d_a, uint64_t(sstride), d_idx, uint32_t(cnt), uint64_t(slen),
                          s.d_b, uint64_t(dss), uint32_t(nv), static_cast<uint8_t *>(nullptr),
                          uint32_t(p.n), uint32_t(cb));
-      good = ok(hipGetLastError(), "scatter launch") &&
-             ok(launch_error_locator(p, d_present, npat, fold, nullptr, s.d_elog, s.stream),
-                "error locator launch") &&
-             ok(launch_reconstruct(p, device_tables(d), s.d_b, slen, dss, d_present, s.d_elog,
-                                   d_pat, cb, s.d_c, dos, scratch, s.stream),
-                "reconstruct launch") &&
-             ok(out_down_lin
-                    ? hipMemcpyAsync(h_out + c0 * ostride, s.d_c, (cb - 1) * ostride + ob, hipMemcpyDeviceToHost,
-                                     s.stream)
-                    : hipMemcpy2DAsync(h_out + c0 * ostride, ostride, s.d_c, dos, ob, cb,
-                                       hipMemcpyDeviceToHost, s.stream),
-                "D2H payloads");
+      good = hip_check(hipGetLastError(), "scatter launch") &&
+             hip_check(launch_error_locator(p, d_present, npat, fold, nullptr, s.d_elog, s.stream),
+                       "error locator launch") &&
+             hip_check(launch_reconstruct(p, device_tables(d), call, scratch, s.stream), "reconstruct launch") &&
+             hip_check(out_down_lin ? hipMemcpyAsync(h_out + c0 * ostride, s.d_c, (cb - 1) * ostride + ob,
+                                                     hipMemcpyDeviceToHost, s.stream)
+                                    : hipMemcpy2DAsync(h_out + c0 * ostride, ostride, s.d_c, dos, ob, cb,
+                                                       hipMemcpyDeviceToHost, s.stream),
+                       "D2H payloads");
     }
-    if (!good) return res(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
+    if (!good) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
   }
   for (Slot &s : pl->slot)
-    if (!ok(hipStreamSynchronize(s.stream), "reconstruct_host_batch"))
-      return res(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
-  return res(NPRS_RESULT_OK);
+    if (!hip_check(hipStreamSynchronize(s.stream), "reconstruct_host_batch"))
+      return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
+  return result(NPRS_RESULT_OK);
 }
 
 }  // extern "C"

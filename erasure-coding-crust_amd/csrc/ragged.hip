@@ -90,12 +90,11 @@ void ragged_check_host(const CodeParams &p, const RaggedItem *items, size_t batc
     }
 }
 
-hipError_t launch_ragged_plan(const CodeParams &p, const RaggedItem *d_items, size_t batch, uint64_t max_len,
-                              bool reconstruct, uint32_t tile, const uint8_t *d_in, uint8_t *d_out, void *ws,
-                              uint32_t *d_status, hipStream_t s) {
-  hipLaunchKernelGGL(ragged_plan, dim3(1), dim3(kPlanThreads), 0, s, d_items, uint32_t(batch), max_len,
-                     reconstruct ? 1 : 0, uint32_t(ilog2(p.k)), tile, d_in, d_out, ragged_first(ws), ragged_tick(ws),
-                     ragged_hdr(ws), d_status);
+hipError_t launch_ragged_plan(const CodeParams &p, const RaggedCall &c, bool reconstruct, uint32_t tile, void *ws,
+                              hipStream_t s) {
+  hipLaunchKernelGGL(ragged_plan, dim3(1), dim3(kPlanThreads), 0, s, c.items, uint32_t(c.batch),
+                     uint64_t(c.max_len), reconstruct ? 1 : 0, uint32_t(ilog2(p.k)), tile, c.in, c.out,
+                     ragged_first(ws), ragged_tick(ws), ragged_hdr(ws), c.status);
   return hipGetLastError();
 }
 
@@ -129,55 +128,39 @@ size_t ragged_systematic_workspace_bytes(const CodeParams &, size_t batch) { ret
 
 size_t ragged_encode_workspace_bytes(const CodeParams &p, size_t batch, size_t max_plen) {
   const size_t own = choose_encode_ragged(p) == RaggedKernel::encode_g_ragged
-                         ? ragged_encode_g_scratch_bytes(p, batch, max_plen)
+                         ? generic_scratch_bytes(p.k, shard_len(p.k, max_plen) / 2, batch)
                          : 0;
   return ragged_scratch_offset(batch) + (own + 255) / 256 * 256;
 }
 
 size_t ragged_reconstruct_workspace_bytes(const CodeParams &p, size_t batch, size_t max_slen) {
   const size_t own = choose_reconstruct_ragged(p) == RaggedKernel::reconstruct_g_ragged
-                         ? ragged_reconstruct_g_scratch_bytes(p, batch, max_slen)
+                         ? generic_scratch_bytes(p.n, max_slen / 2, batch)
                          : gather_order_bytes(p, batch);
   return ragged_scratch_offset(batch) + (own + 255) / 256 * 256;
 }
 
-hipError_t launch_encode_ragged(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,
-                                const RaggedItem *d_items, size_t batch, size_t max_plen, uint8_t *d_shards,
-                                uint32_t *d_status, void *ws, hipStream_t s) {
-  if (const hipError_t e = launch_ragged_plan(p, d_items, batch, max_plen, false, ragged_encode_tile(p),
-                                              d_payloads, d_shards, ws, d_status, s);
-      e != hipSuccess)
-    return e;
-  return choose_encode_ragged(p) == RaggedKernel::encode_k256w_ragged
-             ? launch_encode_k256w_ragged(p, t, batch, max_plen, ws, s)
-             : launch_encode_g_ragged(p, t, d_payloads, d_items, batch, max_plen, d_shards, ws, s);
+hipError_t launch_encode_ragged(const CodeParams &p, const DevTables &t, const RaggedCall &c, void *ws,
+                                hipStream_t s) {
+  if (const hipError_t e = launch_ragged_plan(p, c, false, ragged_encode_tile(p), ws, s); e != hipSuccess) return e;
+  return choose_encode_ragged(p) == RaggedKernel::encode_k256w_ragged ? launch_encode_k256w_ragged(p, t, c, ws, s)
+                                                                       : launch_encode_g_ragged(p, t, c, ws, s);
 }
 
-hipError_t launch_reconstruct_ragged(const CodeParams &p, const DevTables &t, const uint8_t *d_shards,
-                                     const RaggedItem *d_items, const uint8_t *d_present,
-                                     const uint16_t *d_err_log, const uint32_t *d_pattern, size_t batch,
-                                     size_t max_slen, uint8_t *d_out, uint32_t *d_status, void *ws,
+hipError_t launch_reconstruct_ragged(const CodeParams &p, const DevTables &t, const RaggedCall &c, void *ws,
                                      hipStream_t s) {
-  if (const hipError_t e = launch_ragged_plan(p, d_items, batch, max_slen, true, ragged_reconstruct_tile(p),
-                                              d_shards, d_out, ws, d_status, s);
-      e != hipSuccess)
+  if (const hipError_t e = launch_ragged_plan(p, c, true, ragged_reconstruct_tile(p), ws, s); e != hipSuccess)
     return e;
   return choose_reconstruct_ragged(p) == RaggedKernel::reconstruct_n1024x_ragged
-             ? launch_reconstruct_n1024x_ragged(p, t, d_present, d_err_log, d_pattern, batch, max_slen, ws, s)
-             : launch_reconstruct_g_ragged(p, t, d_shards, d_items, d_present, d_err_log, d_pattern, batch,
-                                           max_slen, d_out, ws, s);
+             ? launch_reconstruct_n1024x_ragged(p, t, c, ws, s)
+             : launch_reconstruct_g_ragged(p, t, c, ws, s);
 }
 
-hipError_t launch_systematic_ragged(const CodeParams &p, const uint8_t *d_shards, const RaggedItem *d_items,
-                                    size_t batch, size_t max_slen, uint8_t *d_out, uint32_t *d_status, void *ws,
-                                    hipStream_t s) {
-  if (const hipError_t e = launch_ragged_plan(p, d_items, batch, max_slen, true, ragged_systematic_tile(p), d_shards,
-                                              d_out, ws, d_status, s);
-      e != hipSuccess)
+hipError_t launch_systematic_ragged(const CodeParams &p, const RaggedCall &c, void *ws, hipStream_t s) {
+  if (const hipError_t e = launch_ragged_plan(p, c, true, ragged_systematic_tile(p), ws, s); e != hipSuccess)
     return e;
-  return choose_systematic_ragged(p) == RaggedKernel::systematic_w_ragged
-             ? launch_systematic_w_ragged(p, batch, max_slen, ws, s)
-             : launch_systematic_g_ragged(p, d_shards, d_items, batch, max_slen, d_out, ws, s);
+  return choose_systematic_ragged(p) == RaggedKernel::systematic_w_ragged ? launch_systematic_w_ragged(p, c, ws, s)
+                                                                           : launch_systematic_g_ragged(p, c, ws, s);
 }
 
 }  // namespace ecamd

@@ -62,6 +62,22 @@ struct RaggedHdr {
   uint32_t batch, total;  // total = tile_first[batch]
 };
 
+// One ragged call, built where it enters the library: the input and output
+// buffers the items' offsets are relative to (encode: payloads in, shard rows
+// out; reconstruct and systematic: shard rows in, payloads out), the device
+// item array, the stated maximum length (payload_len for an encode, shard_len
+// otherwise), the nullable status words, and the reconstruct's pattern rows.
+struct RaggedCall {
+  const uint8_t *in;
+  const RaggedItem *items;
+  size_t batch, max_len;
+  uint8_t *out;
+  uint32_t *status;
+  const uint8_t *present = nullptr;  // the reconstruct alone, as in ReconCall
+  const uint16_t *err_log = nullptr;
+  const uint32_t *pattern = nullptr;
+};
+
 // ---- workspace of a ragged call: 256 B of counters (word 0: the tile
 // counter; byte 64: the RaggedHdr), tile_first[batch + 1], then the kernel's
 // own scratch (the gather order of reconstruct_n1024x_ragged; the generic
@@ -104,47 +120,33 @@ size_t ragged_systematic_workspace_bytes(const CodeParams &p, size_t batch);  //
 void ragged_check_host(const CodeParams &p, const RaggedItem *items, size_t batch, uint64_t max_len,
                        bool reconstruct, uint32_t status[2]);
 
-// the plan kernel, in stream order before the call's kernel (d_status
-// nullable); d_in / d_out: the call's input and output buffers (RaggedHdr)
-hipError_t launch_ragged_plan(const CodeParams &p, const RaggedItem *d_items, size_t batch, uint64_t max_len,
-                              bool reconstruct, uint32_t tile, const uint8_t *d_in, uint8_t *d_out, void *ws,
-                              uint32_t *d_status, hipStream_t s);
+// the plan kernel, in stream order before the call's kernel, for tiles of
+// `tile` pieces / columns (c.in / c.out go into the RaggedHdr)
+hipError_t launch_ragged_plan(const CodeParams &p, const RaggedCall &c, bool reconstruct, uint32_t tile, void *ws,
+                              hipStream_t s);
 
 // A ragged call: the plan kernel, then the kernel choose_*_ragged names.  `ws`:
-// the whole workspace (ragged_*_workspace_bytes); d_status nullable.
-hipError_t launch_encode_ragged(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,
-                                const RaggedItem *d_items, size_t batch, size_t max_plen, uint8_t *d_shards,
-                                uint32_t *d_status, void *ws, hipStream_t s);
-hipError_t launch_reconstruct_ragged(const CodeParams &p, const DevTables &t, const uint8_t *d_shards,
-                                     const RaggedItem *d_items, const uint8_t *d_present,
-                                     const uint16_t *d_err_log, const uint32_t *d_pattern, size_t batch,
-                                     size_t max_slen, uint8_t *d_out, uint32_t *d_status, void *ws,
+// the whole workspace (ragged_*_workspace_bytes).  The systematic recovery
+// reads every item's rows y < k (items in the reconstruct's meaning:
+// payload_off in c.out).
+hipError_t launch_encode_ragged(const CodeParams &p, const DevTables &t, const RaggedCall &c, void *ws,
+                                hipStream_t s);
+hipError_t launch_reconstruct_ragged(const CodeParams &p, const DevTables &t, const RaggedCall &c, void *ws,
                                      hipStream_t s);
-// the systematic recovery of every item from its rows y < k (items in the
-// reconstruct's meaning: payload_off in d_out)
-hipError_t launch_systematic_ragged(const CodeParams &p, const uint8_t *d_shards, const RaggedItem *d_items,
-                                    size_t batch, size_t max_slen, uint8_t *d_out, uint32_t *d_status, void *ws,
-                                    hipStream_t s);
+hipError_t launch_systematic_ragged(const CodeParams &p, const RaggedCall &c, void *ws, hipStream_t s);
 // the kernels' own launchers (enc_k256w_ragged.hip, dec_n1024x_ragged.hip,
-// ec_kernels.hip), after the plan on the same stream; the persistent kernels
-// take the buffers and the items from the plan's header
-hipError_t launch_encode_k256w_ragged(const CodeParams &p, const DevTables &t, size_t batch, size_t max_plen,
-                                      void *ws, hipStream_t s);
-hipError_t launch_reconstruct_n1024x_ragged(const CodeParams &p, const DevTables &t, const uint8_t *d_present,
-                                            const uint16_t *d_err_log, const uint32_t *d_pattern, size_t batch,
-                                            size_t max_slen, void *ws, hipStream_t s);
-hipError_t launch_encode_g_ragged(const CodeParams &p, const DevTables &t, const uint8_t *d_payloads,
-                                  const RaggedItem *d_items, size_t batch, size_t max_plen, uint8_t *d_shards,
-                                  void *ws, hipStream_t s);
-hipError_t launch_reconstruct_g_ragged(const CodeParams &p, const DevTables &t, const uint8_t *d_shards,
-                                       const RaggedItem *d_items, const uint8_t *d_present,
-                                       const uint16_t *d_err_log, const uint32_t *d_pattern, size_t batch,
-                                       size_t max_slen, uint8_t *d_out, void *ws, hipStream_t s);
-hipError_t launch_systematic_w_ragged(const CodeParams &p, size_t batch, size_t max_slen, void *ws, hipStream_t s);
-hipError_t launch_systematic_g_ragged(const CodeParams &p, const uint8_t *d_shards, const RaggedItem *d_items,
-                                      size_t batch, size_t max_slen, uint8_t *d_out, void *ws, hipStream_t s);
-size_t ragged_encode_g_scratch_bytes(const CodeParams &p, size_t batch, size_t max_plen);
-size_t ragged_reconstruct_g_scratch_bytes(const CodeParams &p, size_t batch, size_t max_slen);
+// sys_w.hip, ec_kernels.hip), after the plan on the same stream; the persistent
+// kernels take the buffers and the items from the plan's header
+hipError_t launch_encode_k256w_ragged(const CodeParams &p, const DevTables &t, const RaggedCall &c, void *ws,
+                                      hipStream_t s);
+hipError_t launch_reconstruct_n1024x_ragged(const CodeParams &p, const DevTables &t, const RaggedCall &c, void *ws,
+                                            hipStream_t s);
+hipError_t launch_encode_g_ragged(const CodeParams &p, const DevTables &t, const RaggedCall &c, void *ws,
+                                  hipStream_t s);
+hipError_t launch_reconstruct_g_ragged(const CodeParams &p, const DevTables &t, const RaggedCall &c, void *ws,
+                                       hipStream_t s);
+hipError_t launch_systematic_w_ragged(const CodeParams &p, const RaggedCall &c, void *ws, hipStream_t s);
+hipError_t launch_systematic_g_ragged(const CodeParams &p, const RaggedCall &c, void *ws, hipStream_t s);
 
 #if defined(__HIPCC__)
 // A global-memory address that travelled through LDS as two words, back as a

@@ -105,14 +105,13 @@ int ilog2(uint32_t v) { return 31 - __builtin_clz(v); }
 uint32_t systematic_w_cols(const CodeParams &p) { return uint32_t(kSysTileSyms) / (p.k < 256 ? p.k : 256u); }
 uint32_t systematic_w_row_blocks(const CodeParams &p) { return p.k <= 256 ? 1u : p.k / 256; }
 
-hipError_t launch_systematic_w(const CodeParams &p, const uint8_t *d_shards, size_t slen, size_t sstride,
-                               size_t batch, uint8_t *d_out, size_t ostride, void *scratch, hipStream_t s) {
+hipError_t launch_systematic_w(const CodeParams &p, const SysCall &c, void *scratch, hipStream_t s) {
   int cus = 0;
   if (const hipError_t e = prepare_kernel(reinterpret_cast<const void *>(&systematic_w), 0, &cus); e != hipSuccess)
     return e;
   const size_t cols = systematic_w_cols(p);
-  const size_t per_item = (slen / 2 + cols - 1) / cols * systematic_w_row_blocks(p);
-  const size_t tiles = per_item * batch;
+  const size_t per_item = (c.slen / 2 + cols - 1) / cols * systematic_w_row_blocks(p);
+  const size_t tiles = per_item * c.batch;
   const size_t slots = size_t(kSysPerCu) * cus;
   const unsigned grid = unsigned(tiles < slots ? tiles : slots);
   // 32-bit tickets from the counter; a launch past them keeps the static
@@ -121,23 +120,23 @@ hipError_t launch_systematic_w(const CodeParams &p, const uint8_t *d_shards, siz
   uint32_t *tick = tiles > slots && tiles + slots < (size_t(1) << 32) ? static_cast<uint32_t *>(scratch) : nullptr;
   if (tick)
     if (const hipError_t e = launch_zero_counters(tick, sizeof(uint32_t), s); e != hipSuccess) return e;
-  hipLaunchKernelGGL(systematic_w, dim3(grid), dim3(kSysThreads), 0, s, d_shards, uint64_t(slen), uint64_t(sstride),
-                     uint64_t(p.nv) * sstride, ilog2(p.k), d_out, uint64_t(ostride), uint64_t(per_item),
-                     uint64_t(tiles), tick);
+  hipLaunchKernelGGL(systematic_w, dim3(grid), dim3(kSysThreads), 0, s, c.shards, uint64_t(c.slen),
+                     uint64_t(c.sstride), uint64_t(p.nv) * c.sstride, ilog2(p.k), c.out, uint64_t(c.ostride),
+                     uint64_t(per_item), uint64_t(tiles), tick);
   return hipGetLastError();
 }
 
 // `ws` planned by launch_ragged_plan (tile = systematic_w_cols) in stream order
 // before this; the plan zeroes the counter.  The grid is sized from the most
 // tiles the call can have: workgroups past the real count leave at once.
-hipError_t launch_systematic_w_ragged(const CodeParams &p, size_t batch, size_t max_slen, void *ws, hipStream_t s) {
+hipError_t launch_systematic_w_ragged(const CodeParams &p, const RaggedCall &c, void *ws, hipStream_t s) {
   int cus = 0;
   if (!ws) return hipErrorInvalidValue;
   if (const hipError_t e = prepare_kernel(reinterpret_cast<const void *>(&systematic_w_ragged), 0, &cus);
       e != hipSuccess)
     return e;
   const size_t cols = systematic_w_cols(p);
-  const size_t most = (max_slen / 2 + cols - 1) / cols * systematic_w_row_blocks(p) * batch;
+  const size_t most = (c.max_len / 2 + cols - 1) / cols * systematic_w_row_blocks(p) * c.batch;
   if (most + 4096 >= (size_t(1) << 32)) return hipErrorInvalidValue;  // 32-bit tile tickets
   const size_t slots = size_t(kSysPerCu) * cus;
   const unsigned grid = unsigned(most < slots ? most : slots);

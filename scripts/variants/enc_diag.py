@@ -16,7 +16,9 @@ that work costs in the real interleaving:
             for a time account (nobar+static, cmp+static)
     wdyn    every wave takes its own tiles (its 8-piece group of the tile) from a
             counter of its own: no cross-wave tile hand-off, so nobar / cmp
-            stay balanced and valid for timing (nobar+wdyn, cmp+wdyn)
+            stay balanced and valid for timing (nobar+wdyn, cmp+wdyn); the
+            counters' room comes from a widened kTileCounterBytes (wdyn and
+            xwdyn also write OUTDIR/ec_kernels.hpp: pass it to build_var.sh too)
     nbread  only the "regions read out" barriers dropped (tile start, after
             IFFT pass A, before each coset's first exchange)
     nbstg   only the "rows staged" barriers dropped (before each store phase)
@@ -97,7 +99,8 @@ def rep(s, old, new):
 
 ALIAS = {"cmp": ["nobar", "nost", "nold"], "cmpt": ["nobar", "nost", "nold", "notab"]}
 extra = {}
-kinds = [x for part in kind.split("+") for x in ALIAS.get(part, [part])]
+counter_bytes = 256  # kTileCounterBytes (ec_kernels.hpp): every tile counter's block; wdyn / xwdyn widen it
+kinds =[x for part in kind.split("+") for x in ALIAS.get(part, [part])]
 for k in kinds:
     if k == "nobar":
         enc = rep(enc, "const auto rsync = [&]() __attribute__((always_inline)) { lds_barrier(); };",
@@ -118,11 +121,7 @@ for k in kinds:
         # line serialise in L2: ~6 ns per atomic); 1152 B of scratch, zeroed by
         # the shared launch tail: every kernel launched through it gets them
         com = rep(com, "launch_zero_counters(tick, sizeof(uint32_t), s)", "launch_zero_counters(tick, 1152, s)")
-        enc = rep(enc, "size_t k256_scratch_bytes(const CodeParams &) { return 256; }",
-                  "size_t k256_scratch_bytes(const CodeParams &) { return 1152; }")
-        extra["enc_kw.hip"] = rep(open(f"{CS}/enc_kw.hip").read(), "kw_applicable(p) ? 256 : 0", "kw_applicable(p) ? 1152 : 0")
-        extra["enc_k512w.hip"] = rep(open(f"{CS}/enc_k512w.hip").read(), "k512w_applicable(p) ? 256 : 0",
-                                     "k512w_applicable(p) ? 1152 : 0")
+        counter_bytes = max(counter_bytes, 1152)
     elif k == "nbread":
         for old in ("    rsync();  // the other waves are done reading this region (last tile)\n",
                     "    rsync();  // systematic rows read out of the regions\n",
@@ -188,8 +187,8 @@ for k in kinds:
                    "      nxt = {uint32_t(__builtin_amdgcn_readfirstlane(taken))};\n"
                    f"      if ({W}) taken = gridDim.x + atomicAdd(geo.tick + 32 + 32 * (tid0 >> 6), 1u);\n")
         decx = rep(decx, "    if (geo.publishes(tid0)) geo.publish(slot, taken, tid0);\n", "")
-        decx = rep(decx, "return n1024_tick_offset(p, batch) + 256; }", "return n1024_tick_offset(p, batch) + 2048; }")
         decx = rep(decx, "launch_zero_counters(tick, sizeof(uint32_t), s)", "launch_zero_counters(tick, 2048, s)")
+        counter_bytes = max(counter_bytes, 2048)
         extra["dec_n1024x.hip"] = decx
     elif k == "xnoout":
         decx = rep(decx, "        *reinterpret_cast<uint2 *>(O + (col * K + 4 * lane) * 2) = make_uint2(w0, w1);\n",
@@ -236,6 +235,9 @@ open(f"{out}/enc_k256w.hip", "w").write(enc)
 open(f"{out}/enc_w_common.hpp", "w").write(com)
 open(f"{out}/cimg.hpp", "w").write(cim)
 open(f"{out}/dec_n1024.hip", "w").write(dec)
+if counter_bytes != 256:
+    extra["ec_kernels.hpp"] = rep(open(f"{CS}/ec_kernels.hpp").read(), "constexpr size_t kTileCounterBytes = 256;",
+                                  f"constexpr size_t kTileCounterBytes = {counter_bytes};")
 for fname, src in extra.items():
     open(f"{out}/{fname}", "w").write(src)
 print("wrote", out, kinds)

@@ -1079,6 +1079,27 @@ def test_workspace_too_small_is_reported():
     assert bool((d_out == 0x5A).all())
 
 
+def test_encode_ws_large_enough_but_misaligned_is_an_error():
+    """encode_batch_ws on a shape whose scratch is only a tile counter: a short
+    or NULL workspace runs the static schedule, but one that is large enough
+    and not 256-B aligned is an error (alignment is not part of "optional"),
+    and nothing is launched."""
+    import torch
+    nv, plen, batch = 1024, 70_000, 2
+    sl = E.shard_len(nv, plen)
+    need = E.workspace_bytes(nv, plen, batch)[0]
+    assert need == 256
+    d_pay = torch.from_numpy(np.stack([synth.payload(b, plen) for b in range(batch)])).cuda()
+    d_sh = torch.full((batch, nv, sl), 0xAA, dtype=torch.uint8, device="cuda")
+    ws = torch.empty(need + 512, dtype=torch.uint8, device="cuda")[128:]
+    assert ws.data_ptr() % 256 == 128 and ws.numel() >= need
+    with pytest.raises(E.ECError) as e:
+        E.encode_batch_ws(nv, d_pay, plen, plen, batch, d_sh, sl, ws)
+    assert e.value.tag == E.Tag.UNKNOWN_CODE_PARAM and "workspace" in E.last_error()
+    torch.cuda.synchronize()
+    assert bool((d_sh == 0xAA).all())
+
+
 # ------------------------------------------------------- runtime robustness (ADVICE r01)
 def test_scratch_failure_is_reported(oracle):
     """A shape whose per-device scratch cannot be had (here: capped below its

@@ -67,7 +67,9 @@ def strided(buf, base, rows, stride, used):
 
 
 # ---- the uniform call ----------------------------------------------------------
-FORMS = ["plain", "ws", "ws-null"]
+# "ws-misaligned": a workspace large enough but off the 256-B alignment runs the
+# static schedule like a NULL or short one (no error, the workspace untouched)
+FORMS = ["plain", "ws", "ws-null", "ws-misaligned"]
 
 
 def run_uniform(oracle, nv, cols, pad, expect, sh_off=0, out_off=0, ss_odd=0, os_odd=0, batch=3, forms=FORMS):
@@ -80,7 +82,7 @@ def run_uniform(oracle, nv, cols, pad, expect, sh_off=0, out_off=0, ss_odd=0, os
     A = L.Arena(seed=nv * 31 + cols)
     a_sh = A.add("shards", batch * nv * ss, sh_off)
     a_out = {f: A.add("out-" + f, batch * os_, out_off) for f in forms}
-    a_ws = A.add("workspace", max(need, 256))
+    a_ws = A.add("workspace", max(need, 256) + 128)  # (+ 128: the misaligned form's slice)
     host = A.build()
     for b in range(batch):
         strided(host, a_sh + b * nv * ss, k, ss, sl)[:] = ref_rows(oracle, nv, cols, b % 3)[0]
@@ -94,7 +96,8 @@ def run_uniform(oracle, nv, cols, pad, expect, sh_off=0, out_off=0, ss_odd=0, os
         if f == "plain":
             E.systematic_batch(*args)
         else:
-            E.systematic_batch_ws(*args, dev[a_ws: a_ws + need] if f == "ws" and need else None)
+            off = {"ws": 0, "ws-misaligned": 128}.get(f)
+            E.systematic_batch_ws(*args, dev[a_ws + off: a_ws + off + need] if off is not None and need else None)
     got = download(dev)
     for f in forms:
         for b in range(batch):
