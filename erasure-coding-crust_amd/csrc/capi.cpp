@@ -65,9 +65,10 @@ bool encode_host(const CodeParams &p, const uint8_t *payload, size_t len, HostCt
   if (tiny_applicable(p, len, dstride) && out_bytes <= kDirectBytes) {
     // tiny codes and payloads (enc_tiny.hip): the payload rides in the kernel
     // arguments, the rows go straight to the pinned output
-    if (!ensure_host(&c->h_out, &c->h_out_cap, out_bytes)) return false;
+    if (!c->h_out.grow(out_bytes)) return false;
     HostSig sig = call_signal(c);
-    if (!hip_check(launch_encode_tiny(p, device_tables(d), payload, len, c->h_out, dstride, c->stream, &sig),
+    if (!hip_check(launch_encode_tiny(p, device_tables(d), payload, len, c->h_out.get(), dstride, c->stream,
+                                      &sig),
                    "encode launch") ||
         !finish_call(c, "encode", &sig))
       return false;
@@ -75,31 +76,28 @@ bool encode_host(const CodeParams &p, const uint8_t *payload, size_t len, HostCt
     return true;
   }
   if (len + out_bytes <= kDirectBytes) {
-    if (!ensure_host(&c->h_in, &c->h_in_cap, len) || !ensure_host(&c->h_out, &c->h_out_cap, out_bytes))
+    if (!c->h_in.grow(len) || !c->h_out.grow(out_bytes))
       return false;
     ScratchLease lease(d, encode_scratch_bytes(p, len, 1), c->stream);
     if (!lease.ok()) return false;
-    std::memcpy(c->h_in, payload, len);
+    std::memcpy(c->h_in.get(), payload, len);
     HostSig sig = call_signal(c);  // stored by the encode kernel itself when it can (HostSig)
-    const EncodeCall call{c->h_in, len, len, 1, c->h_out, dstride};
+    const EncodeCall call{c->h_in.get(), len, len, 1, c->h_out.get(), dstride};
     if (!hip_check(launch_encode(p, device_tables(d), call, lease.ptr(), c->stream, &sig), "encode launch") ||
         !finish_call(c, "encode", &sig))
       return false;
     *sl_out = sl;
     return true;
   }
-  if (!ensure_host(&c->h_in, &c->h_in_cap, len) ||
-      !ensure_dev(reinterpret_cast<void **>(&c->d_in), &c->d_in_cap, len) ||
-      !ensure_host(&c->h_out, &c->h_out_cap, out_bytes) ||
-      !ensure_dev(reinterpret_cast<void **>(&c->d_out), &c->d_out_cap, size_t(p.nv) * dstride))
+  if (!c->h_in.grow(len) || !c->d_in.grow(len) || !c->h_out.grow(out_bytes) || !c->d_out.grow(out_bytes))
     return false;
   ScratchLease lease(d, encode_scratch_bytes(p, len, 1), c->stream);
   if (!lease.ok()) return false;
-  std::memcpy(c->h_in, payload, len);
-  const EncodeCall call{c->d_in, len, len, 1, c->d_out, dstride};
-  if (!hip_check(hipMemcpyAsync(c->d_in, c->h_in, len, hipMemcpyHostToDevice, c->stream), "H2D") ||
+  std::memcpy(c->h_in.get(), payload, len);
+  const EncodeCall call{c->d_in.get(), len, len, 1, c->d_out.get(), dstride};
+  if (!hip_check(hipMemcpyAsync(c->d_in.get(), c->h_in.get(), len, hipMemcpyHostToDevice, c->stream), "H2D") ||
       !hip_check(launch_encode(p, device_tables(d), call, lease.ptr(), c->stream), "encode launch") ||
-      !hip_check(hipMemcpyAsync(c->h_out, c->d_out, out_bytes, hipMemcpyDeviceToHost, c->stream),
+      !hip_check(hipMemcpyAsync(c->h_out.get(), c->d_out.get(), out_bytes, hipMemcpyDeviceToHost, c->stream),
                  "D2H") ||
       !hip_check(hipStreamSynchronize(c->stream), "encode"))
     return false;
@@ -113,18 +111,16 @@ bool reconstruct_host(const CodeParams &p, const std::vector<uint8_t> &present, 
   DeviceState *d = device_state();
   if (!d) return false;
   const size_t out_bytes = sl * p.k, dstride = dev_pitch(sl);
-  if (!ensure_dev(reinterpret_cast<void **>(&c->d_in), &c->d_in_cap, size_t(p.nv) * dstride) ||
-      !ensure_dev(reinterpret_cast<void **>(&c->d_out), &c->d_out_cap, out_bytes) ||
-      !ensure_host(&c->h_out, &c->h_out_cap, out_bytes))
+  if (!c->d_in.grow(size_t(p.nv) * dstride) || !c->d_out.grow(out_bytes) || !c->h_out.grow(out_bytes))
     return false;
   bool all_systematic = true;
   for (uint32_t y = 0; y < p.k; ++y) all_systematic &= present[y] != 0;
   // small calls: the kernels read the staged shards and write the payload
   // in pinned host memory (kDirectBytes)
   const bool direct = size_t(p.nv) * dstride + out_bytes <= kDirectBytes;
-  const uint8_t *src = direct ? c->h_in : c->d_in;
-  uint8_t *dst = direct ? c->h_out : c->d_out;
-  if (!direct && !hip_check(hipMemcpyAsync(c->d_in, c->h_in, size_t(p.nv) * dstride,
+  const uint8_t *src = direct ? c->h_in.get() : c->d_in.get();
+  uint8_t *dst = direct ? c->h_out.get() : c->d_out.get();
+  if (!direct && !hip_check(hipMemcpyAsync(c->d_in.get(), c->h_in.get(), size_t(p.nv) * dstride,
                                            hipMemcpyHostToDevice, c->stream),
                             "H2D"))
     return false;
@@ -136,13 +132,14 @@ bool reconstruct_host(const CodeParams &p, const std::vector<uint8_t> &present, 
   const auto finish = [&](bool launched) {
     return launched &&
            (direct ||
-            hip_check(hipMemcpyAsync(c->h_out, c->d_out, out_bytes, hipMemcpyDeviceToHost, c->stream), "D2H")) &&
+            hip_check(hipMemcpyAsync(c->h_out.get(), c->d_out.get(), out_bytes, hipMemcpyDeviceToHost, c->stream),
+                      "D2H")) &&
            (direct ? finish_call(c, "reconstruct", &sig) : hip_check(hipStreamSynchronize(c->stream), "reconstruct"));
   };
   if (all_systematic && direct && systematic_tiny_applicable(p, sl))
     // tiny calls: the k systematic shards ride in the kernel arguments (enc_tiny.hip)
     return finish(
-        hip_check(launch_systematic_tiny(p, c->h_in, sl, dstride, dst, c->stream, &sig), "systematic launch"));
+        hip_check(launch_systematic_tiny(p, c->h_in.get(), sl, dstride, dst, c->stream, &sig), "systematic launch"));
   if (all_systematic) {
     // every systematic shard is present: decode == interleave (exact)
     // (one payload: no tile counter, systematic_w's static schedule)
@@ -173,7 +170,7 @@ bool reconstruct_host(const CodeParams &p, const std::vector<uint8_t> &present, 
 bool take_output(HostCtx *c, size_t bytes, DataBlock *out) {
   uint8_t *buf = static_cast<uint8_t *>(std::malloc(bytes ? bytes : 1));
   if (!buf) return false;
-  std::memcpy(buf, c->h_out, bytes);
+  std::memcpy(buf, c->h_out.get(), bytes);
   out->array = buf;
   out->length = bytes;
   return true;
@@ -231,7 +228,7 @@ NPRSResult ECCR_obtain_chunks(unsigned long nv, const DataBlock *message, Chunks
   if (!chunks) return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
   for (unsigned long v = 0; v < nv; ++v) {
     uint8_t *b = static_cast<uint8_t *>(std::malloc(sl));
-    std::memcpy(b, c->h_out + v * dev_pitch(sl), sl);
+    std::memcpy(b, c->h_out.get() + v * dev_pitch(sl), sl);
     chunks[v].data.array = b;
     chunks[v].data.length = sl;
     chunks[v].index = v;
@@ -277,10 +274,10 @@ NPRSResult ECCR_reconstruct(unsigned long nv, const ChunksList *input, DataBlock
     }
   if (count < p.k) return result(NPRS_RESULT_NOT_ENOUGH_CHUNKS);  // reed-solomon.hpp:99-100
   HostCtx *c = host_ctx();
-  if (!c || !ensure_host(&c->h_in, &c->h_in_cap, size_t(nv) * dev_pitch(sl)))
+  if (!c || !c->h_in.grow(size_t(nv) * dev_pitch(sl)))
     return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
   for (unsigned long v = 0; v < nv; ++v)
-    if (slot[v]) std::memcpy(c->h_in + v * dev_pitch(sl), slot[v]->data.array, sl);
+    if (slot[v]) std::memcpy(c->h_in.get() + v * dev_pitch(sl), slot[v]->data.array, sl);
   if (!reconstruct_host(p, present, sl, c) || !take_output(c, sl * p.k, outdata))
     return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
   return result(NPRS_RESULT_OK);
@@ -313,19 +310,18 @@ NPRSResult ECCR_reconstruct_from_systematic(unsigned long nv, const ChunksList *
   // rows staged at a 16-B pitch, like every other staged layout (systematic_w's loads)
   const size_t pitch = dev_pitch(used);
   const size_t in_bytes = size_t(p.k) * pitch, out_bytes = used * p.k;
-  if (!c || !d || !ensure_host(&c->h_in, &c->h_in_cap, in_bytes) ||
-      !ensure_host(&c->h_out, &c->h_out_cap, out_bytes) ||
-      !ensure_dev(reinterpret_cast<void **>(&c->d_in), &c->d_in_cap, in_bytes) ||
-      !ensure_dev(reinterpret_cast<void **>(&c->d_out), &c->d_out_cap, out_bytes))
+  if (!c || !d || !c->h_in.grow(in_bytes) || !c->h_out.grow(out_bytes) || !c->d_in.grow(in_bytes) ||
+      !c->d_out.grow(out_bytes))
     return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
-  for (uint32_t y = 0; y < p.k; ++y) std::memcpy(c->h_in + y * pitch, slot[y]->data.array, used);
+  for (uint32_t y = 0; y < p.k; ++y) std::memcpy(c->h_in.get() + y * pitch, slot[y]->data.array, used);
   CodeParams pk = p;
   pk.nv = p.k;  // staged layout holds only the k systematic shards
-  if (!hip_check(hipMemcpyAsync(c->d_in, c->h_in, in_bytes, hipMemcpyHostToDevice, c->stream),
+  if (!hip_check(hipMemcpyAsync(c->d_in.get(), c->h_in.get(), in_bytes, hipMemcpyHostToDevice, c->stream),
                  "H2D") ||
-      !hip_check(launch_systematic(pk, SysCall{c->d_in, used, pitch, 1, c->d_out, out_bytes}, nullptr, c->stream),
+      !hip_check(launch_systematic(pk, SysCall{c->d_in.get(), used, pitch, 1, c->d_out.get(), out_bytes}, nullptr,
+                                   c->stream),
                  "systematic launch") ||
-      !hip_check(hipMemcpyAsync(c->h_out, c->d_out, out_bytes, hipMemcpyDeviceToHost, c->stream),
+      !hip_check(hipMemcpyAsync(c->h_out.get(), c->d_out.get(), out_bytes, hipMemcpyDeviceToHost, c->stream),
                  "D2H") ||
       !hip_check(hipStreamSynchronize(c->stream), "systematic") ||
       !take_output(c, out_bytes, outdata))
@@ -349,8 +345,7 @@ NPRSResult ECCR_Test_MeasurePerformance(const DataBlock *message, unsigned long 
      // hipHostMalloc), as the reference builds its encoders outside its timed
      // regions (src/erasure_coding.rs:190-207)
     const size_t pitch_bytes = size_t(nv) * dev_pitch(shard_len(p.k, message->length));
-    if (!ensure_host(&c->h_out, &c->h_out_cap, pitch_bytes) ||
-        !ensure_host(&c->h_in, &c->h_in_cap, std::max(pitch_bytes, size_t(message->length))))
+    if (!c->h_out.grow(pitch_bytes) || !c->h_in.grow(std::max(pitch_bytes, size_t(message->length))))
       return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
     (void)call_signal(c);
   }
@@ -359,9 +354,9 @@ NPRSResult ECCR_Test_MeasurePerformance(const DataBlock *message, unsigned long 
     return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
   const auto t1 = clk::now();
   // reconstruct from all shards (src/erasure_coding.rs:200-211)
-  if (!ensure_host(&c->h_in, &c->h_in_cap, size_t(nv) * dev_pitch(sl)))
+  if (!c->h_in.grow(size_t(nv) * dev_pitch(sl)))
     return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
-  std::memcpy(c->h_in, c->h_out, size_t(nv) * dev_pitch(sl));
+  std::memcpy(c->h_in.get(), c->h_out.get(), size_t(nv) * dev_pitch(sl));
   std::vector<uint8_t> present(p.n, 0);
   for (unsigned long v = 0; v < nv; ++v) present[v] = 1;
   const auto t2 = clk::now();

@@ -1,5 +1,5 @@
 // cimg.hpp — multiply tables from the element-indexed compact image
-// (ec_kernels.hpp kCImg*, DevTables::cimg) resident at LDS address 0, for
+// (table_images.hpp kCImg*, DevTables::cimg) resident at LDS address 0, for
 // the two-workgroups-per-CU encodes (enc_w_common.hpp).  Kernels using it
 // declare no static LDS (prepare_kernel checks), so the image starts at
 // absolute LDS address 0.

@@ -14,19 +14,21 @@
 
 namespace ecamd {
 
+// Device memory owned by a DeviceState: freed with a state that is destroyed
+// (a failed set-up; a published state never is, see g_dev).
+struct HipFree {
+  void operator()(void *p) const { (void)hipFree(p); }
+};
+template <typename T>
+using DevPtr = std::unique_ptr<T, HipFree>;
+
 struct DeviceState {
   int id = -1;
-  uint16_t *skews = nullptr;
-  MulTab *mtab = nullptr;
-  MulTab *mtab_t = nullptr;  // mtab_tin, then mtab_tout
-  uint8_t *timg_t = nullptr;
-  uint8_t *timg_f9 = nullptr;
-  uint8_t *cimg = nullptr;
-  uint8_t *eimg512 = nullptr;
-  uint8_t *eimg256 = nullptr;
-  MulTab *mslot = nullptr;  // mtab by skew slot (DevTables::mslot)
+  DevPtr<uint16_t> skews;
+  DevPtr<MulTab> mtab, mtab_t, mslot;  // mtab_t: mtab_tin, then mtab_tout; mslot: mtab by skew slot
+  DevPtr<uint8_t> timg_t, timg_f9, cimg, eimg512, eimg256;
   std::mutex mu;
-  std::map<uint32_t, uint16_t *> fold;
+  std::map<uint32_t, DevPtr<uint16_t>> fold;
   std::mutex scratch_mu;  // held by a ScratchLease
   void *scratch = nullptr;
   size_t scratch_cap = 0;
@@ -59,10 +61,14 @@ std::mutex g_mu;
 // destructors at process exit can crash or hang; process teardown reclaims them
 std::vector<std::unique_ptr<DeviceState>> &g_dev = *new std::vector<std::unique_ptr<DeviceState>>();
 
-bool hip_ok(hipError_t e, const char *what) {
-  if (e == hipSuccess) return true;
-  set_error(std::string("erasure_coding_crust(amd): ") + what + ": " + hipGetErrorString(e));
-  return false;
+// `bytes` of device memory for `owner`, filled from `data` (if any); false (error set) on failure
+template <typename T>
+bool upload(DevPtr<T> &owner, const void *data, size_t bytes, const char *what) {
+  void *p = nullptr;
+  if (!hip_check(hipMalloc(&p, bytes), (std::string("hipMalloc(") + what + ")").c_str())) return false;
+  owner.reset(static_cast<T *>(p));
+  return !data ||
+         hip_check(hipMemcpy(p, data, bytes, hipMemcpyHostToDevice), (std::string("upload ") + what).c_str());
 }
 }  // namespace
 
@@ -83,7 +89,7 @@ DeviceState *device_state() {
               "there is no CPU fallback)");
     return nullptr;
   }
-  if (!hip_ok(hipGetDevice(&dev), "hipGetDevice")) return nullptr;
+  if (!hip_check(hipGetDevice(&dev), "hipGetDevice")) return nullptr;
   std::lock_guard<std::mutex> lk(g_mu);
   if (g_dev.size() < size_t(count)) g_dev.resize(count);
   auto &slot = g_dev[dev];
@@ -91,119 +97,31 @@ DeviceState *device_state() {
   const Field &f = field();
   auto st = std::make_unique<DeviceState>();
   st->id = dev;
-  if (!hip_ok(hipMalloc(&st->skews, f.skews.size() * 2), "hipMalloc(skews)")) return nullptr;
-  if (!hip_ok(hipMalloc(&st->mtab, f.mtab.size() * sizeof(MulTab)), "hipMalloc(mtab)"))
+  // the LDS and element-indexed table images (table_images.hpp), then the
+  // multiply tables by skew slot (the generic kernels: one load per table)
+  const std::vector<uint8_t> cimg = compact_image(f), e256 = eimg256_images(f), e512 = eimg512_images(f),
+                             f9 = f9_images(f), tower = tower_images(f);
+  const std::vector<MulTab> ms = mslot_tables(f);
+  if (cimg.empty() || f9.empty()) {
+    set_error("erasure_coding_crust(amd): a table image's constant has no F9 table");
     return nullptr;
-  if (!hip_ok(hipMemcpy(st->skews, f.skews.data(), f.skews.size() * 2, hipMemcpyHostToDevice),
-              "upload skews") ||
-      !hip_ok(hipMemcpy(st->mtab, f.mtab.data(), f.mtab.size() * sizeof(MulTab),
-                        hipMemcpyHostToDevice),
-              "upload mtab"))
-    return nullptr;
-  // LDS table images (ec_kernels.hpp kTabImages), LdsTabs<1024>::addr layout:
-  // the tower images (subfield tables at stages >= tower_sub_min(q))
-  std::vector<uint8_t> img_t(kTabImages * kTabImageBytes, 0);
-  for (int q = 0; q < kTabImages; ++q)
-    for (uint32_t i = 0; i < 1023; ++i) {
-      const uint32_t c = f.skews[1024 * q + i];
-      const uint32_t sw = (i ^ (i >> 4) ^ (i >> 8)) & 15;
-      const size_t slot = size_t(q) * kTabImageBytes + ((i >> 4) << 8) + (sw << 4);
-      if (__builtin_ctz(1024 * q + i + 1) >= tower_sub_min(q)) {
-        const MulTabSub u = f.sub_tab(c);
-        std::memcpy(&img_t[slot], &u.w[0], 16);
-        std::memcpy(&img_t[slot + 16384], &u.w[4], 4);
-      } else {
-        const MulTab g = f.tower_tab(c);
-        for (uint32_t plane = 0; plane < 5; ++plane)
-          std::memcpy(&img_t[slot + plane * 16384], reinterpret_cast<const uint8_t *>(&g) + 16 * plane, 16);
-      }
-    }
-  std::vector<uint8_t> img_f9(kF9Images * kTabImageBytes, 0);
-  for (int kind = 0; kind < kF9Images; ++kind) {
-    std::memcpy(&img_f9[size_t(kind) * kTabImageBytes], img_t.data(), kTabImageBytes);
-    for (uint32_t i = 0; i < 1023; ++i) {
-      if (!f9_slot(kind, i)) continue;
-      MulTabF9 t9;
-      if (!f.f9_tab(f.skews[i], &t9)) return nullptr;  // (tower_check: never)
-      const uint32_t sw = (i ^ (i >> 4) ^ (i >> 8)) & 15;
-      const size_t slot = size_t(kind) * kTabImageBytes + ((i >> 4) << 8) + (sw << 4);
-      for (uint32_t plane = 0; plane < 4; ++plane)
-        std::memcpy(&img_f9[slot + plane * 16384], &t9.w[4 * plane], 16);
-    }
   }
-  // the element-indexed compact image (ec_kernels.hpp): entry x = element 2 x
-  std::vector<uint8_t> cimg(kCImgBytes, 0);
-  for (uint32_t x = 0; x < 512; ++x) {
-    const uint32_t e = 2 * x, c = e == 0 ? kZeroTab : f.log[e];
-    if (x < 128) {
-      const MulTabSub u = f.sub_tab(c);
-      std::memcpy(&cimg[kCImgSub0 | cimg_lin(x)], &u.w[0], 16);
-      std::memcpy(&cimg[kCImgSub1 | cimg_lin(x)], &u.w[4], 4);
-    } else if (x < 256) {
-      MulTabF9 t9;
-      if (!f.f9_tab(c, &t9)) return nullptr;  // (tower(e) >> 8 == 1 for 256 <= e < 512)
-      for (uint32_t q = 0; q < 4; ++q)
-        std::memcpy(&cimg[(kCImgF9 + q * kCImgF9Plane) | cimg_lin(x ^ 128)], &t9.w[4 * q], 16);
-    } else {
-      const MulTab g = f.tower_tab(c);
-      for (uint32_t q = 0; q < 5; ++q)
-        std::memcpy(&cimg[(kCImgGen + q * kCImgGenPlane) | cimg_lin(x ^ 256)], &g.w[4 * q], 16);
-    }
-  }
-  if (!hip_ok(hipMalloc(&st->cimg, cimg.size()), "hipMalloc(compact image)") ||
-      !hip_ok(hipMemcpy(st->cimg, cimg.data(), cimg.size(), hipMemcpyHostToDevice),
-              "upload compact image"))
-    return nullptr;
-  // the k = 512 encode's per-coset extension images (ec_kernels.hpp kEImg512*):
-  // general tower tables of the elements x = (512 j >> (m + 1)) + e
-  std::vector<uint8_t> eimg(kEImg512Cosets * kEImg512Bytes, 0);
-  for (uint32_t j = 1; j <= kEImg512Cosets; ++j)
-    for (uint32_t m = 0; m < 3; ++m)
-      for (uint32_t e = 0; e < (256u >> m); ++e) {
-        const uint32_t x = ((512 * j) >> (m + 1)) + e;
-        const MulTab g = f.tower_tab(f.log[2 * x]);
-        for (uint32_t q = 0; q < 5; ++q)
-          std::memcpy(&eimg[(j - 1) * kEImg512Bytes + kEImg512Stage[m] + q * (4096 >> m) + cimg_lin(e)],
-                      &g.w[4 * q], 16);
-      }
-  std::vector<uint8_t> eimg256(kEImg256Cosets * kEImg256Bytes, 0);
-  for (uint32_t j = 4; j < 4 + kEImg256Cosets; ++j)
-    for (uint32_t e = 0; e < 128; ++e) {
-      const MulTab g = f.tower_tab(f.log[2 * (128 * j + e)]);
-      for (uint32_t q = 0; q < 5; ++q)
-        std::memcpy(&eimg256[(j - 4) * kEImg256Bytes + q * 2048 + cimg_lin(e)], &g.w[4 * q], 16);
-    }
-  if (!hip_ok(hipMalloc(&st->eimg256, eimg256.size()), "hipMalloc(k256 coset images)") ||
-      !hip_ok(hipMemcpy(st->eimg256, eimg256.data(), eimg256.size(), hipMemcpyHostToDevice),
-              "upload k256 coset images"))
-    return nullptr;
-  if (!hip_ok(hipMalloc(&st->eimg512, eimg.size()), "hipMalloc(k512 coset images)") ||
-      !hip_ok(hipMemcpy(st->eimg512, eimg.data(), eimg.size(), hipMemcpyHostToDevice),
-              "upload k512 coset images"))
-    return nullptr;
-  if (!hip_ok(hipMalloc(&st->timg_f9, img_f9.size()), "hipMalloc(F9 images)") ||
-      !hip_ok(hipMemcpy(st->timg_f9, img_f9.data(), img_f9.size(), hipMemcpyHostToDevice),
-              "upload F9 images"))
-    return nullptr;
-  if (!hip_ok(hipMalloc(&st->timg_t, img_t.size()), "hipMalloc(tower images)") ||
-      !hip_ok(hipMemcpy(st->timg_t, img_t.data(), img_t.size(), hipMemcpyHostToDevice),
-              "upload tower images"))
-    return nullptr;
-  {  // the multiply tables by skew slot (the generic kernels: one load per table)
-    std::vector<MulTab> ms(f.skews.size());
-    for (size_t i = 0; i < ms.size(); ++i) ms[i] = f.mtab[f.skews[i]];
-    if (!hip_ok(hipMalloc(&st->mslot, ms.size() * sizeof(MulTab)), "hipMalloc(mslot)") ||
-        !hip_ok(hipMemcpy(st->mslot, ms.data(), ms.size() * sizeof(MulTab), hipMemcpyHostToDevice),
-                "upload mslot"))
-      return nullptr;
-  }
-  if (!hip_ok(hipMalloc(&st->mtab_t, 2 * f.mtab.size() * sizeof(MulTab)), "hipMalloc(tower mtab)") ||
-      !hip_ok(hipMemcpy(st->mtab_t, f.mtab_tin.data(), f.mtab_tin.size() * sizeof(MulTab),
-                        hipMemcpyHostToDevice),
-              "upload mtab_tin") ||
-      !hip_ok(hipMemcpy(st->mtab_t + f.mtab.size(), f.mtab_tout.data(),
-                        f.mtab_tout.size() * sizeof(MulTab), hipMemcpyHostToDevice),
-              "upload mtab_tout"))
+  const size_t mtab_bytes = f.mtab.size() * sizeof(MulTab);
+  // a failure frees what was uploaded before it (st's members) and leaves the slot empty
+  if (!upload(st->skews, f.skews.data(), f.skews.size() * 2, "skews") ||
+      !upload(st->mtab, f.mtab.data(), mtab_bytes, "mtab") ||
+      !upload(st->cimg, cimg.data(), cimg.size(), "compact image") ||
+      !upload(st->eimg256, e256.data(), e256.size(), "k256 coset images") ||
+      !upload(st->eimg512, e512.data(), e512.size(), "k512 coset images") ||
+      !upload(st->timg_f9, f9.data(), f9.size(), "F9 images") ||
+      !upload(st->timg_t, tower.data(), tower.size(), "tower images") ||
+      !upload(st->mslot, ms.data(), ms.size() * sizeof(MulTab), "mslot") ||
+      !upload(st->mtab_t, nullptr, 2 * mtab_bytes, "tower mtab") ||  // one buffer: mtab_tin, then mtab_tout
+      !hip_check(hipMemcpy(st->mtab_t.get(), f.mtab_tin.data(), mtab_bytes, hipMemcpyHostToDevice),
+                 "upload mtab_tin") ||
+      !hip_check(hipMemcpy(st->mtab_t.get() + f.mtab.size(), f.mtab_tout.data(), mtab_bytes,
+                           hipMemcpyHostToDevice),
+                 "upload mtab_tout"))
     return nullptr;
   // load the library's code object now (the first kernel launch of a process
   // loads it, ~1 ms): one one-lane launch, so no C-ABI call's timed region
@@ -220,29 +138,27 @@ DeviceState *device_state() {
 
 DevTables device_tables(DeviceState *d) {
   DevTables t;
-  t.skews = d->skews;
-  t.mtab = d->mtab;
-  t.mtab_tin = d->mtab_t;
-  t.mtab_tout = d->mtab_t + kFieldSize;
-  t.timg_t = d->timg_t;
-  t.timg_f9 = d->timg_f9;
-  t.cimg = d->cimg;
-  t.mslot = d->mslot;
-  t.eimg512 = d->eimg512;
-  t.eimg256 = d->eimg256;
+  t.skews = d->skews.get();
+  t.mtab = d->mtab.get();
+  t.mtab_tin = d->mtab_t.get();
+  t.mtab_tout = d->mtab_t.get() + kFieldSize;
+  t.timg_t = d->timg_t.get();
+  t.timg_f9 = d->timg_f9.get();
+  t.cimg = d->cimg.get();
+  t.mslot = d->mslot.get();
+  t.eimg512 = d->eimg512.get();
+  t.eimg256 = d->eimg256.get();
   return t;
 }
 
 const uint16_t *device_fold(DeviceState *d, uint32_t n) {
   std::lock_guard<std::mutex> lk(d->mu);
   auto it = d->fold.find(n);
-  if (it != d->fold.end()) return it->second;
+  if (it != d->fold.end()) return it->second.get();
   std::vector<uint16_t> F = field().fold_log_walsh(n);
-  uint16_t *p = nullptr;
-  if (!hip_ok(hipMalloc(&p, n * 2), "hipMalloc(fold)")) return nullptr;
-  if (!hip_ok(hipMemcpy(p, F.data(), n * 2, hipMemcpyHostToDevice), "upload fold")) return nullptr;
-  d->fold[n] = p;
-  return p;
+  DevPtr<uint16_t> p;
+  if (!upload(p, F.data(), n * 2, "fold")) return nullptr;
+  return (d->fold[n] = std::move(p)).get();
 }
 
 hipError_t prepare_kernel(const void *fn, int lds_bytes, int *cus) {
@@ -300,7 +216,7 @@ ScratchLease::ScratchLease(DeviceState *d, size_t bytes, hipStream_t stream)
     }
     d->scratch = nullptr;
     d->scratch_cap = 0;
-    if (!hip_ok(hipMalloc(&d->scratch, bytes), "hipMalloc(scratch)")) return;
+    if (!hip_check(hipMalloc(&d->scratch, bytes), "hipMalloc(scratch)")) return;
     d->scratch_cap = bytes;
   } else if (d->scratch_used) {
     (void)hipStreamWaitEvent(stream, d->scratch_done, 0);
@@ -360,7 +276,7 @@ std::shared_ptr<const Locator> cached_locator(DeviceState *d, const CodeParams &
         ++d->loc_hits;
         // not done: the creating call is still in flight (it marks the entry
         // under this lock before returning), so `ready`'s stream is alive
-        if (!hit->done && !hip_ok(hipStreamWaitEvent(stream, hit->ready, 0), "locator wait")) return nullptr;
+        if (!hit->done && !hip_check(hipStreamWaitEvent(stream, hit->ready, 0), "locator wait")) return nullptr;
         return hit;
       }
     ++d->loc_misses;
@@ -381,22 +297,22 @@ std::shared_ptr<const Locator> cached_locator(DeviceState *d, const CodeParams &
     (void)hipEventDestroy(L->ready);
     L->ready = nullptr;
     L->done = false;
-    if (!hip_ok(hipEventCreateWithFlags(&L->ready, hipEventDisableTiming), "hipEventCreate")) return nullptr;
+    if (!hip_check(hipEventCreateWithFlags(&L->ready, hipEventDisableTiming), "hipEventCreate")) return nullptr;
   } else {
     L = std::make_shared<Locator>();
     L->cap_n = p.n;
-    if (!hip_ok(hipMalloc(&L->d_present, p.n), "hipMalloc(locator)") ||
-        !hip_ok(hipMalloc(&L->d_elog, size_t(p.n) * 2), "hipMalloc(locator)") ||
-        !hip_ok(hipEventCreateWithFlags(&L->ready, hipEventDisableTiming), "hipEventCreate"))
+    if (!hip_check(hipMalloc(&L->d_present, p.n), "hipMalloc(locator)") ||
+        !hip_check(hipMalloc(&L->d_elog, size_t(p.n) * 2), "hipMalloc(locator)") ||
+        !hip_check(hipEventCreateWithFlags(&L->ready, hipEventDisableTiming), "hipEventCreate"))
       return nullptr;
   }
   L->nv = p.nv;
   L->present = present;
-  if (!hip_ok(hipMemcpyAsync(L->d_present, L->present.data(), p.n, hipMemcpyHostToDevice, stream),
+  if (!hip_check(hipMemcpyAsync(L->d_present, L->present.data(), p.n, hipMemcpyHostToDevice, stream),
               "H2D present") ||
-      !hip_ok(launch_error_locator(p, L->d_present, 1, fold, nullptr, L->d_elog, stream),
+      !hip_check(launch_error_locator(p, L->d_present, 1, fold, nullptr, L->d_elog, stream),
               "error locator launch") ||
-      !hip_ok(hipEventRecord(L->ready, stream), "hipEventRecord")) {
+      !hip_check(hipEventRecord(L->ready, stream), "hipEventRecord")) {
     (void)hipStreamSynchronize(stream);  // nothing issued above may outlive L
     return nullptr;
   }
@@ -470,12 +386,12 @@ StreamScratch::StreamScratch(DeviceState *d, hipStream_t s, size_t bytes) : want
     // every earlier holder on this stream has finished enqueueing (they held
     // mu), so once the stream drains nothing reads the smaller buffer
     if (e_->p) {
-      if (!hip_ok(hipStreamSynchronize(s), "scratch grow sync")) return;
+      if (!hip_check(hipStreamSynchronize(s), "scratch grow sync")) return;
       (void)hipFree(e_->p);
     }
     e_->p = nullptr;
     e_->cap = 0;
-    if (!hip_ok(hipMalloc(&e_->p, bytes), "hipMalloc(stream scratch)")) return;
+    if (!hip_check(hipMalloc(&e_->p, bytes), "hipMalloc(stream scratch)")) return;
     e_->cap = bytes;
   }
   p_ = e_->p;
@@ -536,30 +452,6 @@ void locator_cache_stats(DeviceState *d, unsigned long *hits, unsigned long *mis
   if (misses) *misses = d->loc_misses;
 }
 
-bool ensure_host(uint8_t **p, size_t *cap, size_t need) {
-  if (*cap >= need && *p) return true;
-  if (*p) (void)hipHostFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  size_t sz = need < 4096 ? 4096 : need + need / 4;
-  if (!hip_ok(hipHostMalloc(reinterpret_cast<void **>(p), sz, hipHostMallocDefault),
-              "hipHostMalloc"))
-    return false;
-  *cap = sz;
-  return true;
-}
-
-bool ensure_dev(void **p, size_t *cap, size_t need) {
-  if (*cap >= need && *p) return true;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  size_t sz = need < 4096 ? 4096 : need + need / 4;
-  if (!hip_ok(hipMalloc(p, sz), "hipMalloc")) return false;
-  *cap = sz;
-  return true;
-}
-
 HostCtx::~HostCtx() {
   // the thread's work is finished (every C-ABI call synchronises its stream);
   // release on the context's own device
@@ -571,12 +463,10 @@ HostCtx::~HostCtx() {
     forget_stream(device, stream);
     (void)hipStreamDestroy(stream);
   }
-  for (uint8_t *h : {h_in, h_out})
-    if (h) (void)hipHostFree(h);
+  // here, on the context's device, not in the members' destructors after the switch back
+  h_in.release(), h_out.release();
   if (h_flag) (void)hipHostFree(h_flag);
-  for (void *p : {static_cast<void *>(d_in), static_cast<void *>(d_out),
-                  static_cast<void *>(d_present), static_cast<void *>(d_elog)})
-    if (p) (void)hipFree(p);
+  d_in.release(), d_out.release();
   if (switched) (void)hipSetDevice(cur);
 }
 
@@ -599,7 +489,7 @@ HostSig call_signal(HostCtx *c) {
 }
 
 bool finish_call(HostCtx *c, const char *what, const HostSig *sig) {
-  const auto sync = [&]() { return hip_ok(hipStreamSynchronize(c->stream), what); };
+  const auto sync = [&]() { return hip_check(hipStreamSynchronize(c->stream), what); };
   const HostSig s = sig ? *sig : call_signal(c);
   if (!s.flag) return sync();
   const uint32_t v = s.v;
@@ -613,7 +503,7 @@ bool finish_call(HostCtx *c, const char *what, const HostSig *sig) {
       if (__atomic_load_n(c->h_flag, __ATOMIC_ACQUIRE) == v) {
         if (!probe) return true;
         const hipError_t e = hipStreamQuery(c->stream);
-        return e == hipSuccess || e == hipErrorNotReady || hip_ok(e, what);
+        return e == hipSuccess || e == hipErrorNotReady || hip_check(e, what);
       }
     if (std::chrono::duration<double, std::micro>(clk::now() - t0).count() > kFinishSpinUs)
       return sync();  // long calls block instead of spinning; errors surface here
@@ -629,7 +519,7 @@ HostCtx *host_ctx() {
   if (ctx && ctx->device == d->id) return ctx.get();
   ctx = std::make_unique<HostCtx>();
   ctx->device = d->id;
-  if (!hip_ok(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking), "hipStreamCreate")) {
+  if (!hip_check(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking), "hipStreamCreate")) {
     ctx.reset();
     return nullptr;
   }

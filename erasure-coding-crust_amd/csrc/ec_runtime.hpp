@@ -127,19 +127,58 @@ void locator_done(DeviceState *d, const Locator &L);
 void locator_drop(DeviceState *d, const Locator &L);
 void locator_cache_stats(DeviceState *d, unsigned long *hits, unsigned long *misses);
 
+void set_error(const std::string &msg);  // also printed to stderr
+const char *last_error();
+// false, with the thread's last error set to `what` and HIP's text, unless e is hipSuccess
+inline bool hip_check(hipError_t e, const char *what) {
+  if (e == hipSuccess) return true;
+  set_error(std::string("erasure_coding_crust(amd): ") + what + ": " + hipGetErrorString(e));
+  return false;
+}
+
+// A growable buffer with one owner: device memory, or (Pinned) pinned host
+// memory.  The destructor releases on whatever device is current; an owner
+// bound to a device calls release() with that device current.
+template <typename T, bool Pinned = false>
+class Buffer {
+ public:
+  Buffer() = default;
+  Buffer(const Buffer &) = delete;
+  Buffer &operator=(const Buffer &) = delete;
+  ~Buffer() { release(); }
+  T *get() const { return p_; }
+  // at least `bytes`: the buffer as it is if large enough, else a new one with a quarter of headroom (the
+  // old one freed without synchronising: its owner's work on it is finished); false, error set and empty on failure
+  bool grow(size_t bytes) {
+    if (cap_ >= bytes && p_) return true;
+    release();
+    const size_t sz = bytes < 4096 ? 4096 : bytes + bytes / 4;
+    void *p = nullptr;
+    if (!(Pinned ? hip_check(hipHostMalloc(&p, sz, hipHostMallocDefault), "hipHostMalloc")
+                 : hip_check(hipMalloc(&p, sz), "hipMalloc")))
+      return false;
+    p_ = static_cast<T *>(p);
+    cap_ = sz;
+    return true;
+  }
+  void release() {
+    if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_));
+    p_ = nullptr;
+    cap_ = 0;
+  }
+
+ private:
+  T *p_ = nullptr;
+  size_t cap_ = 0;
+};
+
 // Growable buffers of one host thread (reentrancy = the reference's
 // thread_local scratch, reed-solomon.hpp:198-201).
-struct HostCtx {
-  HostCtx() = default;
-  HostCtx(const HostCtx &) = delete;
-  HostCtx &operator=(const HostCtx &) = delete;
-  ~HostCtx();  // synchronises and releases the stream and every buffer
+struct HostCtx {  // (not copyable: its buffers are not)
+  ~HostCtx();    // synchronises and releases the stream and every buffer
   hipStream_t stream = nullptr;
-  uint8_t *h_in = nullptr, *h_out = nullptr;  // pinned
-  size_t h_in_cap = 0, h_out_cap = 0;
-  uint8_t *d_in = nullptr, *d_out = nullptr, *d_present = nullptr;
-  uint16_t *d_elog = nullptr;
-  size_t d_in_cap = 0, d_out_cap = 0, d_present_cap = 0, d_elog_cap = 0;
+  Buffer<uint8_t, true> h_in, h_out;  // pinned
+  Buffer<uint8_t> d_in, d_out;
   int device = -1;
   uint32_t *h_flag = nullptr;  // pinned completion word (finish_call)
   uint32_t seq = 0;
@@ -170,20 +209,8 @@ bool finish_call(HostCtx *c, const char *what, const HostSig *sig = nullptr);
 // the next completion word / value of this context (flag null if the pinned
 // word could not be allocated: finish_call then synchronises the stream)
 HostSig call_signal(HostCtx *c);
-bool ensure_host(uint8_t **p, size_t *cap, size_t need);
-bool ensure_dev(void **p, size_t *cap, size_t need);
-
-void set_error(const std::string &msg);  // also printed to stderr
-const char *last_error();
 
 // ---- shared by the C-ABI files (capi.cpp, host_pipeline.hip)
-// false, with the thread's last error set to `what` and HIP's text, unless e is hipSuccess
-inline bool hip_check(hipError_t e, const char *what) {
-  if (e == hipSuccess) return true;
-  set_error(std::string("erasure_coding_crust(amd): ") + what + ": " + hipGetErrorString(e));
-  return false;
-}
-
 inline NPRSResult result(NPRSResult_Tag tag) {
   NPRSResult r;
   std::memset(&r, 0, sizeof r);

@@ -7,7 +7,7 @@
 // wave-private LDS exchanges, tower coordinates with subfield / F9 / general
 // multiplies.  What differs:
 //  * the multiply tables are the 32 KB element-indexed compact image
-//    (ec_kernels.hpp kCImg*, DevTables::cimg) instead of the 80 KB skew-slot
+//    (table_images.hpp kCImg*, DevTables::cimg) instead of the 80 KB skew-slot
 //    image, so a workgroup needs 64 KB of LDS and TWO are resident per CU.
 //    Each workgroup still synchronises its waves at every staging step, but
 //    while one waits at a barrier, for its payload loads or for its row

@@ -199,7 +199,7 @@ struct Rows {
 };
 
 // coset j's extension image -> LDS by LDS-DMA, chunk i (1 KB) by wave i % 8:
-// chunks 0..19 = stage 0, 20..34 = stages 1, 2 (ec_kernels.hpp kEImg512Stage)
+// chunks 0..19 = stage 0, 20..34 = stages 1, 2 (table_images.hpp kEImg512Stage)
 __device__ __forceinline__ void dma_ext(const uint8_t *eimg, uint32_t j, uint32_t wave, uint32_t lane) {
   const uint8_t *src = eimg + (j - 1) * kEImg512Bytes + 16 * lane;
   const uint32_t n = ext_chunks(j);

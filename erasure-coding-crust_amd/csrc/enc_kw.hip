@@ -30,7 +30,7 @@ namespace {
 constexpr uint32_t XCH0 = kCImgBytes;        // the wave regions follow the tables
 constexpr uint32_t SLOT = XCH0 + WAVES * XCH_BYTES;  // the next tile's index
 // k = 256 (n = 2048 only): the extension tables of cosets 4..7 (stage 0,
-// elements 512..1023: ec_kernels.hpp kEImg256*) after the slot
+// elements 512..1023: table_images.hpp kEImg256*) after the slot
 constexpr uint32_t EXT8 = SLOT + 1024;
 template <int M>
 constexpr int lds_bytes() { return int(M == 8 ? EXT8 + kEImg256Bytes : SLOT + 16); }

@@ -52,19 +52,18 @@ __global__ void __launch_bounds__(256) scatter_present(const uint8_t *__restrict
 
 struct Slot {
   hipStream_t stream = nullptr;
-  uint8_t *d_a = nullptr, *d_b = nullptr, *d_c = nullptr;
-  uint16_t *d_elog = nullptr;
+  Buffer<uint8_t> d_a, d_b, d_c;
+  Buffer<uint16_t> d_elog;
   // a chunk's pattern index ([cb] u32), its shards' indices ([cb][cnt]
   // u16) and its distinct present rows ([npat][n]) in one device buffer,
   // uploaded by ONE copy from the pinned h_meta (until round 6: three copies,
   // two of them from pageable vectors, beside the shards' copy)
-  uint8_t *d_meta = nullptr, *h_meta = nullptr;
-  size_t cap_meta = 0, cap_h_meta = 0;
+  Buffer<uint8_t> d_meta;
+  Buffer<uint8_t, true> h_meta;
   // the slot's own kernel scratch (k = 1024 encode coefficients, reconstruct
   // gather orders): stream-ordered by the slot, so the three slots overlap; a
   // shared per-device lease would order them behind each other
-  uint8_t *d_scr = nullptr;
-  size_t cap_a = 0, cap_b = 0, cap_c = 0, cap_elog = 0, cap_scr = 0;
+  Buffer<uint8_t> d_scr;
   // host staging of a chunk's distinct erasure patterns (h_rows, then copied
   // into h_meta); `staged` is recorded after h_meta's upload so the next chunk
   // on this slot does not overwrite it early
@@ -88,12 +87,11 @@ struct Pipeline {
         (void)hipStreamDestroy(s.stream);
       }
       if (s.staged) (void)hipEventDestroy(s.staged);
-      for (void *p : {static_cast<void *>(s.d_a), static_cast<void *>(s.d_b), static_cast<void *>(s.d_c),
-                      static_cast<void *>(s.d_meta), static_cast<void *>(s.d_elog),
-                      static_cast<void *>(s.d_scr)})
-        if (p) (void)hipFree(p);
-      if (s.h_meta) (void)hipHostFree(s.h_meta);
-      s = Slot{};
+      // here, on the slots' device (the members' destructors run on whichever is current)
+      s.d_a.release(), s.d_b.release(), s.d_c.release(), s.d_meta.release(), s.d_elog.release();
+      s.d_scr.release(), s.h_meta.release();
+      s.stream = nullptr;  // reusable: the thread may come back to this device
+      s.staged = nullptr;
     }
     if (switched) (void)hipSetDevice(cur);
     device = -1;
@@ -129,18 +127,10 @@ Pipeline *pipeline() {  // one per host thread (reentrant like the reference)
   return &pl;
 }
 
-template <typename T>
-bool grow(T **p, size_t *cap, size_t bytes) {
-  return ensure_dev(reinterpret_cast<void **>(p), cap, bytes);
-}
-
 // the slot's scratch for `bytes` (nullptr and true when none is needed)
 bool slot_scratch(Slot &s, size_t bytes, void **out) {
-  *out = nullptr;
-  if (bytes == 0) return true;
-  if (!grow(&s.d_scr, &s.cap_scr, bytes)) return false;
-  *out = s.d_scr;
-  return true;
+  *out = bytes && s.d_scr.grow(bytes) ? s.d_scr.get() : nullptr;
+  return bytes == 0 || *out;
 }
 
 uint64_t mix64(uint64_t x) {  // splitmix64 finaliser (pattern hash terms)
@@ -198,7 +188,7 @@ NPRSResult ECCR_AMD_encode_host_batch(unsigned long nv, const uint8_t *h_payload
   for (unsigned long c0 = 0, i = 0; c0 < batch; c0 += chunk, ++i) {
     Slot &s = pl->slot[i % kSlots];
     const size_t cb = batch - c0 < chunk ? batch - c0 : chunk;
-    if (!grow(&s.d_a, &s.cap_a, chunk * dps) || !grow(&s.d_b, &s.cap_b, chunk * nv * dss))
+    if (!s.d_a.grow(chunk * dps) || !s.d_b.grow(chunk * nv * dss))
       return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
     void *scratch = nullptr;
     if (!slot_scratch(s, encode_scratch_bytes(p, plen, cb), &scratch))
@@ -206,19 +196,19 @@ NPRSResult ECCR_AMD_encode_host_batch(unsigned long nv, const uint8_t *h_payload
     const uint8_t *hp = h_payloads + c0 * pstride;
     uint8_t *hs = h_shards + c0 * nv * sstride;
     const hipError_t up =
-        pay_lin ? hipMemcpyAsync(s.d_a, hp, (cb - 1) * pstride + plen, hipMemcpyHostToDevice, s.stream)
-                : hipMemcpy2DAsync(s.d_a, dps, hp, pstride, plen, cb, hipMemcpyHostToDevice, s.stream);
-    const EncodeCall call{s.d_a, plen, dps, cb, s.d_b, dss};
+        pay_lin ? hipMemcpyAsync(s.d_a.get(), hp, (cb - 1) * pstride + plen, hipMemcpyHostToDevice, s.stream)
+                : hipMemcpy2DAsync(s.d_a.get(), dps, hp, pstride, plen, cb, hipMemcpyHostToDevice, s.stream);
+    const EncodeCall call{s.d_a.get(), plen, dps, cb, s.d_b.get(), dss};
     if (!hip_check(up, "H2D payloads") ||
         (sh_pre &&
-         !hip_check(hipMemcpyAsync(s.d_b, hs, (cb * nv - 1) * sstride + sl, hipMemcpyHostToDevice, s.stream),
+         !hip_check(hipMemcpyAsync(s.d_b.get(), hs, (cb * nv - 1) * sstride + sl, hipMemcpyHostToDevice, s.stream),
                     "H2D shard rows' surroundings")) ||
         !hip_check(launch_encode(p, device_tables(d), call, scratch, s.stream), "encode launch"))
       return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
     const hipError_t down =
-        sh_down_lin ? hipMemcpyAsync(hs, s.d_b, (cb * nv - 1) * sstride + sl, hipMemcpyDeviceToHost,
+        sh_down_lin ? hipMemcpyAsync(hs, s.d_b.get(), (cb * nv - 1) * sstride + sl, hipMemcpyDeviceToHost,
                                      s.stream)
-                    : hipMemcpy2DAsync(hs, sstride, s.d_b, dss, sl, cb * nv, hipMemcpyDeviceToHost,
+                    : hipMemcpy2DAsync(hs, sstride, s.d_b.get(), dss, sl, cb * nv, hipMemcpyDeviceToHost,
                                        s.stream);
     if (!hip_check(down, "D2H shards"))
       return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
@@ -287,20 +277,19 @@ NPRSResult ECCR_AMD_reconstruct_host_batch(unsigned long nv, const uint8_t *h_sh
     // h_meta / d_meta: [pattern index | shard indices | present rows], each part 256-B aligned
     const size_t pat_bytes = (chunk * 4 + 255) / 256 * 256, idx_bytes = (chunk * cnt * 2 + 255) / 256 * 256;
     const size_t rows_at = pat_bytes + idx_bytes;
-    if (!grow(&s.d_a, &s.cap_a, chunk * cnt * sstride) || !grow(&s.d_b, &s.cap_b, chunk * nv * dss) ||
-        !grow(&s.d_c, &s.cap_c, chunk * dos) || !grow(&s.d_meta, &s.cap_meta, rows_at + chunk * p.n) ||
-        !grow(&s.d_elog, &s.cap_elog, chunk * p.n * 2))
+    if (!s.d_a.grow(chunk * cnt * sstride) || !s.d_b.grow(chunk * nv * dss) || !s.d_c.grow(chunk * dos) ||
+        !s.d_meta.grow(rows_at + chunk * p.n) || !s.d_elog.grow(chunk * p.n * 2))
       return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
-    uint32_t *d_pat = reinterpret_cast<uint32_t *>(s.d_meta);
-    const uint16_t *d_idx = reinterpret_cast<const uint16_t *>(s.d_meta + pat_bytes);
-    uint8_t *d_present = s.d_meta + rows_at;
+    uint32_t *d_pat = reinterpret_cast<uint32_t *>(s.d_meta.get());
+    const uint16_t *d_idx = reinterpret_cast<const uint16_t *>(s.d_meta.get() + pat_bytes);
+    uint8_t *d_present = s.d_meta.get() + rows_at;
     // distinct erasure patterns of the chunk: one present
     // row and one locator each; payload b uses row h_pat[b]
     if (!hip_check(hipEventSynchronize(s.staged), "staging reuse")) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
-    if (!ensure_host(&s.h_meta, &s.cap_h_meta, rows_at + chunk * p.n))
+    if (!s.h_meta.grow(rows_at + chunk * p.n))
       return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
-    std::memcpy(s.h_meta + pat_bytes, h_index + c0 * cnt, cb * cnt * 2);
-    uint32_t *h_pat = reinterpret_cast<uint32_t *>(s.h_meta);
+    std::memcpy(s.h_meta.get() + pat_bytes, h_index + c0 * cnt, cb * cnt * 2);
+    uint32_t *h_pat = reinterpret_cast<uint32_t *>(s.h_meta.get());
     s.h_rows.clear();
     s.h_rows.reserve(cb * p.n);
     // hash -> first pattern with it; further ones chained through next_pat
@@ -339,34 +328,34 @@ NPRSResult ECCR_AMD_reconstruct_host_batch(unsigned long nv, const uint8_t *h_sh
       }
       h_pat[j] = uint32_t(found);
     }
-    std::memcpy(s.h_meta + rows_at, s.h_rows.data(), size_t(npat) * p.n);
+    std::memcpy(s.h_meta.get() + rows_at, s.h_rows.data(), size_t(npat) * p.n);
     void *scratch = nullptr;
     if (!slot_scratch(s, reconstruct_scratch_bytes(p, slen, cb), &scratch))
       return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
-    const ReconCall call{s.d_b, slen, dss, d_present, s.d_elog, d_pat, cb, s.d_c, dos};
+    const ReconCall call{s.d_b.get(), slen, dss, d_present, s.d_elog.get(), d_pat, cb, s.d_c.get(), dos};
     bool good =
-        hip_check(hipMemcpyAsync(s.d_a, h_shards + c0 * cnt * sstride, cb * cnt * sstride,
+        hip_check(hipMemcpyAsync(s.d_a.get(), h_shards + c0 * cnt * sstride, cb * cnt * sstride,
                                  hipMemcpyHostToDevice, s.stream),
                   "H2D shards") &&
-        hip_check(hipMemcpyAsync(s.d_meta, s.h_meta, rows_at + size_t(npat) * p.n, hipMemcpyHostToDevice,
+        hip_check(hipMemcpyAsync(s.d_meta.get(), s.h_meta.get(), rows_at + size_t(npat) * p.n, hipMemcpyHostToDevice,
                                  s.stream),
                   "H2D patterns") &&
         hip_check(hipEventRecord(s.staged, s.stream), "staging event") &&
-        (!out_pre || hip_check(hipMemcpyAsync(s.d_c, h_out + c0 * ostride, (cb - 1) * ostride + ob,
+        (!out_pre || hip_check(hipMemcpyAsync(s.d_c.get(), h_out + c0 * ostride, (cb - 1) * ostride + ob,
                                               hipMemcpyHostToDevice, s.stream),
                                "H2D out rows' surroundings"));
     if (good) {
       hipLaunchKernelGGL(scatter_present, dim3(unsigned(cnt), unsigned(cb < 65535 ? cb : 65535)), dim3(256),
-                         0, s.stream, s.d_a, uint64_t(sstride), d_idx, uint32_t(cnt), uint64_t(slen),
-                         s.d_b, uint64_t(dss), uint32_t(nv), static_cast<uint8_t *>(nullptr),
+                         0, s.stream, s.d_a.get(), uint64_t(sstride), d_idx, uint32_t(cnt), uint64_t(slen),
+                         s.d_b.get(), uint64_t(dss), uint32_t(nv), static_cast<uint8_t *>(nullptr),
                          uint32_t(p.n), uint32_t(cb));
       good = hip_check(hipGetLastError(), "scatter launch") &&
-             hip_check(launch_error_locator(p, d_present, npat, fold, nullptr, s.d_elog, s.stream),
+             hip_check(launch_error_locator(p, d_present, npat, fold, nullptr, s.d_elog.get(), s.stream),
                        "error locator launch") &&
              hip_check(launch_reconstruct(p, device_tables(d), call, scratch, s.stream), "reconstruct launch") &&
-             hip_check(out_down_lin ? hipMemcpyAsync(h_out + c0 * ostride, s.d_c, (cb - 1) * ostride + ob,
+             hip_check(out_down_lin ? hipMemcpyAsync(h_out + c0 * ostride, s.d_c.get(), (cb - 1) * ostride + ob,
                                                      hipMemcpyDeviceToHost, s.stream)
-                                    : hipMemcpy2DAsync(h_out + c0 * ostride, ostride, s.d_c, dos, ob, cb,
+                                    : hipMemcpy2DAsync(h_out + c0 * ostride, ostride, s.d_c.get(), dos, ob, cb,
                                                        hipMemcpyDeviceToHost, s.stream),
                        "D2H payloads");
     }

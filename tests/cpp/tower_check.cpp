@@ -5,7 +5,7 @@
 // ec_device.hpp) byte for
 // byte and checks every table kind against the field, and runs the additive
 // FFT / IFFT (additive_fft.hpp:99-141) in tower coordinates with the tower
-// image rule (ec_kernels.hpp tower_sub_min) against the plain transform.
+// image rule (table_images.hpp tower_sub_min) against the plain transform.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "gf_field.hpp"
+#include "table_images.hpp"
 
 using namespace ecamd;
 
@@ -123,20 +124,19 @@ int main() {
     }
   }
   CHECK(nf9 >= 512, "f9 constants %d", nf9);
-  // the F9 image rule (ec_kernels.hpp f9_slot): image 0's stage-1 entries
+  // the F9 image rule (table_images.hpp f9_slot): image 0's stage-1 entries
   // (i = 1 mod 4) and, in the encode's image, its stage-0 entries 256..510
   // have high tower coordinate <= 1
   for (uint32_t i = 0; i < 1023; ++i) {
     MulTabF9 t9;
-    if (i % 4 == 1 || (i % 2 == 0 && i >= 256 && i < 512)) CHECK(f.f9_tab(f.skews[i], &t9), "f9 slot %u", i);
+    if (f9_slot(1, i)) CHECK(f.f9_tab(f.skews[i], &t9), "f9 slot %u", i);
   }
   // the tower image rule: every entry at a stage >= tower_sub_min(q) is a
-  // subfield skew (ec_kernels.hpp; mirrored here)
-  const auto sub_min = [](int q) { return q == 0 ? 2 : q == 1 ? 3 : 4; };
+  // subfield skew (table_images.hpp)
   for (int q = 0; q < 4; ++q)
     for (uint32_t i = 0; i < 1023; ++i) {
       const uint32_t idx = 1024 * q + i, c = f.skews[idx];
-      if (__builtin_ctz(idx + 1) >= sub_min(q)) CHECK(c == kZeroTab || f.exp[c] < 256, "q=%d i=%u", q, i);
+      if (__builtin_ctz(idx + 1) >= tower_sub_min(q)) CHECK(c == kZeroTab || f.exp[c] < 256, "q=%d i=%u", q, i);
     }
   // alias slots (enc_k256.hip PassIdx, dec_n1024.hip sub_alias): the skew of
   // position p at stage m of the transform at index off (a multiple of 2^(m+1))
@@ -168,9 +168,9 @@ int main() {
       const auto mulp = [&](uint16_t x, uint32_t skew_i, int tower) -> uint16_t {
         const uint32_t c = f.skews[skew_i], i = skew_i - index;
         if (!tower) return apply(mul_acc, f.mtab[c], x);
-        if (__builtin_ctz(skew_i + 1) >= sub_min(q)) return apply(mul_acc_sub, f.sub_tab(c), x);
+        if (__builtin_ctz(skew_i + 1) >= tower_sub_min(q)) return apply(mul_acc_sub, f.sub_tab(c), x);
         MulTabF9 tf;
-        if (tower == 2 && q == 0 && (i % 4 == 1 || (i % 2 == 0 && i >= 256 && i < 512)) && f.f9_tab(c, &tf))
+        if (tower == 2 && q == 0 && f9_slot(1, i) && f.f9_tab(c, &tf))
           return apply(mul_acc_f9, tf, x);
         return apply(mul_acc, f.tower_tab(c), x);
       };
