@@ -59,8 +59,7 @@ struct RaggedGeo {
   };
   static constexpr int kWords = 11;
   // the words are read and written as LDS (ds instructions), not through the
-  // body's generic pointer (flat instructions)
-  using LdsWord = __attribute__((address_space(3))) volatile uint32_t;
+  // body's generic pointer (flat instructions): LdsWord, ec_device.hpp
   __device__ static __forceinline__ LdsWord *lds_words(volatile uint32_t *slot) { return (LdsWord *)slot; }
   struct Pre {
     uint64_t total;  // tiles of the launch

@@ -72,6 +72,10 @@ __device__ __forceinline__ uint2 lds_ld2(uint32_t a) {
 __device__ __forceinline__ void lds_st2(uint32_t a, uint2 v) {
   *(__attribute__((address_space(3))) uint64_t *)(uintptr_t(a)) = (uint64_t(v.y) << 32) | v.x;
 }
+// a word of an LDS slot one thread writes and every wave reads after a barrier
+// (the persistent kernels' tile tickets): ds instructions, never cached in a
+// register across the barrier
+using LdsWord = __attribute__((address_space(3))) volatile uint32_t;
 
 // One LDS-DMA wave-instruction: 16 B per lane from `src` (per lane) to the
 // wave's 1 KB of LDS at `dst` (wave-uniform: M0) + 16 lane.  Inline asm

@@ -15,8 +15,8 @@
 //    (phase stamps of the 16-wave form: 30% of wave time at barriers, 9% in
 //    the payload loads, 9% in the stores);
 //  * the tile is 64 pieces (8 waves x 8), each shard row a 128-B segment.
-// The passes, the payload fetch, the row stores and the launch tail are shared
-// with enc_kw.hip and enc_k512w.hip: enc_w_common.hpp.  The tile body itself
+// The passes, the payload fetch, the row stores, the tile schedule and the launch
+// tail are shared with enc_kw.hip and enc_k512w.hip: enc_w_common.hpp.  The tile body itself
 // is in enc_k256w_body.hpp, shared with encode_k256w_ragged.
 #include "enc_k256w_body.hpp"
 
@@ -30,7 +30,7 @@ __global__ void __launch_bounds__(THREADS, 4) encode_k256w(const uint8_t *__rest
                                                            uint64_t sstride, int nv, uint32_t batch,
                                                            const uint8_t *__restrict__ cimg,
                                                            uint32_t *__restrict__ tick) {
-  const k256w::UniformGeo geo{payloads, plen, pstride, shards, slen, sstride, nv, batch, tick};
+  const UniformGeo<k256w::TILE> geo{payloads, plen, pstride, shards, slen, sstride, nv, batch, tick};
 #include "enc_k256w_tile.inc"
 }
 
@@ -38,7 +38,7 @@ hipError_t launch_encode_k256w(const CodeParams &p, const DevTables &t, const En
                                hipStream_t s) {
   if (!t.cimg) return hipErrorInvalidValue;
   if (p.nv <= 2 * k256w::K || p.nv > 1024) return hipErrorInvalidValue;  // cosets 256, 512 (, 768)
-  return launch_w(encode_k256w, k256w::lds_bytes<k256w::UniformGeo>(), k256w::TILE, p, c, scratch, s, t.cimg);
+  return launch_w(encode_k256w, k256w::lds_bytes<UniformGeo<k256w::TILE>>(), k256w::TILE, p, c, scratch, s, t.cimg);
 }
 
 }  // namespace ecamd

@@ -1,40 +1,11 @@
 // enc_k256w_body.hpp — what the k = 256, n = 1024 encode's one kernel body
 // (enc_k256w_tile.inc) needs at namespace scope: its LDS map,
-// staging swizzle, row-store geometry and the geometry policies.  The body is
-// shared by encode_k256w (enc_k256w.hip: the uniform batch) and
-// encode_k256w_ragged (enc_k256w_ragged.hip: items of unequal length,
-// ragged.hpp).  It is parameterised by a geometry policy that
-// says, for a tile ticket, which payload bytes, shard rows, piece count and
-// pitch the tile works on, and how the ticket travels from the thread that
-// takes it to the other waves.  The transforms, the staging, the row stores
-// and the order of barriers do not depend on it.
-//
-// A geometry policy Geo provides (all values wave-uniform):
-//   Tile, ticket(T)         what a wave keeps of a ticket between reading it
-//                           from LDS and the end of its tile; ticket(T) <
-//                           Pre::total means a tile of the launch
-//   SLOT_BYTES              LDS bytes at SLOT the policy publishes tickets in
-//   Pre, prepare()          what the policy works out once per launch; total:
-//                           the launch's tiles
-//   publishes(tid0)         the threads that take part in publishing a ticket
-//                           (thread 0, or all of wave 0); the call sites are
-//                           reached by whole waves, wave 0 always among them
-//   first(slot, tid0)       those threads: take and publish the workgroup's
-//                           first ticket
-//   next_ticket(T)          thread 0: the ticket after tile T's
-//   publish(slot, ticket, tid0)
-//                           those threads: resolve and store thread 0's ticket
-//   read(slot).t            the published Tile (after a barrier)
-//   Loc, loc(pre, T)        where a valid tile's payload bytes are, as far as
-//                           it is worked out when the tile is read
-//   loc_or_none(pre, T)     the same for a tile that may be past the end: then
-//                           a place for which the fetch loads nothing
-//   fetch(pre, Loc)         the payload fetch's geometry (Fetch)
-//   At, at(pre, T), piece0(At), rows(At), npieces(pre, T), sstride(T)
-//                           geometry of a valid tile's transforms and stores
+// staging swizzle and row-store geometry.  The body is shared by encode_k256w
+// (enc_k256w.hip: the uniform batch) and encode_k256w_ragged
+// (enc_k256w_ragged.hip: items of unequal length, ragged.hpp).  It is
+// parameterised by a geometry policy (enc_w_common.hpp: the contract, the
+// ticket protocol, and the uniform batch's UniformGeo).
 #pragma once
-
-#include <type_traits>
 
 #include "enc_w_common.hpp"
 
@@ -80,73 +51,6 @@ struct Rows {
     return {v0, c, XCH0 + c * XCH_BYTES + soff8(v0, c)};
   }
   __device__ static __forceinline__ v4u read(uint32_t a, int it) { return lds_r128(a ^ soff8(uint32_t(it) * VSTEP, 0)); }
-};
-
-using LdsWord = __attribute__((address_space(3))) volatile uint32_t;
-
-// what the payload fetch of a tile needs: the item's payload, its length in
-// bytes and pieces, the tile's first piece
-struct Fetch {
-  const uint8_t *P;
-  uint64_t plen, npieces, piece0;
-};
-
-// The uniform batch: payload b at b * pstride, its rows at b * nv * sstride,
-// every payload plen bytes: ticket cur is tile cur % tiles_pp of payload
-// cur / tiles_pp.  Without a counter (no scratch) a static grid stride
-// (slower: the two workgroups of a CU drift apart).
-struct UniformGeo {
-  const uint8_t *payloads;
-  uint64_t plen_, pstride;
-  uint8_t *shards;
-  uint64_t slen, sstride_;
-  int nv;
-  uint32_t batch;
-  uint32_t *tick;
-  using Tile = uint32_t;  // the ticket itself
-  static constexpr uint32_t SLOT_BYTES = 16;
-  struct Pre {  // per launch: pieces and tiles per payload, tiles of the launch
-    uint64_t npieces;
-    uint32_t tiles_pp, total;
-  };
-  __device__ __forceinline__ Pre prepare() const {
-    const uint64_t npieces = slen / 2;
-    const uint32_t tiles_pp = uint32_t((npieces + TILE - 1) / TILE);
-    return {npieces, tiles_pp, tiles_pp * batch};  // < 2^32 (launch_encode_k256w)
-  }
-  __device__ __forceinline__ bool publishes(uint32_t tid0) const { return tid0 == 0; }
-  __device__ __forceinline__ void first(LdsWord *slot, uint32_t) const {
-    *slot = tick ? atomicAdd(tick, 1u) : blockIdx.x;
-  }
-  __device__ __forceinline__ uint32_t next_ticket(Tile c) const {
-    return tick ? atomicAdd(tick, 1u) : c + gridDim.x;
-  }
-  __device__ __forceinline__ void publish(LdsWord *slot, uint32_t ticket, uint32_t) const { *slot = ticket; }
-  struct Read {
-    Tile t;
-  };
-  __device__ __forceinline__ Read read(LdsWord *slot) const { return {uint32_t(__builtin_amdgcn_readfirstlane(*slot))}; }
-  __device__ __forceinline__ uint32_t ticket(Tile c) const { return c; }
-  struct Loc {
-    uint64_t b, i;  // payload, tile in the payload
-  };
-  __device__ __forceinline__ Loc loc(const Pre &p, Tile c) const { return {c / p.tiles_pp, c % p.tiles_pp}; }
-  // past the end: the zero path, no loads
-  __device__ __forceinline__ Loc loc_or_none(const Pre &p, Tile c) const {
-    return {c < p.total ? uint64_t(c / p.tiles_pp) : uint64_t(0),
-            uint64_t(c < p.total ? c % p.tiles_pp : p.tiles_pp)};
-  }
-  __device__ __forceinline__ Fetch fetch(const Pre &p, Loc l) const {
-    return {payloads + l.b * pstride, plen_, p.npieces, l.i * TILE};
-  }
-  struct At {
-    uint64_t b, piece0;  // a valid tile's payload and first piece
-  };
-  __device__ __forceinline__ At at(const Pre &p, Tile c) const { return {c / p.tiles_pp, uint64_t(c % p.tiles_pp) * TILE}; }
-  __device__ __forceinline__ uint64_t piece0(At a) const { return a.piece0; }
-  __device__ __forceinline__ uint64_t npieces(const Pre &p, Tile) const { return p.npieces; }
-  __device__ __forceinline__ uint64_t sstride(Tile) const { return sstride_; }
-  __device__ __forceinline__ uint8_t *rows(At a) const { return shards + a.b * uint64_t(nv) * sstride_; }
 };
 
 }  // namespace k256w

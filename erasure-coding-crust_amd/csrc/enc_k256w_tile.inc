@@ -8,7 +8,7 @@
 // in the kernel, encode_k256w's code is what it was before the body was shared.
 //
 // In scope at the point of inclusion:
-//   geo        the geometry policy object (enc_k256w_body.hpp)
+//   geo        the geometry policy object (contract: enc_w_common.hpp)
 //   nv, cimg   as encode_k256w's parameters of these names
 // and no other declaration of the names this fragment declares.
 {
@@ -25,16 +25,7 @@
   const auto pre = geo.prepare();
   const uint32_t total = pre.total;
   const uint32_t wave_s = __builtin_amdgcn_readfirstlane(tid0 >> 6);
-  // Dynamic schedule: tiles are taken from the launch's counter (zeroed
-  // before the launch) one tile ahead, so the two workgroups of a CU,
-  // which the issue arbiter serves at unequal rates (the older one's waves win
-  // ties), finish together.  With a static grid-stride split the faster one
-  // ended up to 2.8 ms before the slower one of a 7 ms launch, which then ran
-  // alone (scripts/variants/clk_run.py, DESIGN.md §5.1).
-  // Thread 0 takes tile t + 1 at the start of tile t and the policy publishes
-  // it in the LDS slot after the tile's systematic stores; every wave reads it
-  // after the barrier that follows IFFT pass A; the slot is rewritten only
-  // after the next tile-start barrier, by which every wave has read it.
+  // (the ticket protocol -- taken, published, read, rewritten: enc_w_common.hpp)
   Tile cur = geo.read(slot).t;
 
   // This lane's 4 x 16 payload bytes of a tile: pieces piece0 + 8 wave +
@@ -89,27 +80,20 @@
     // multiples of 16: the uniform dispatch's alignment test, the ragged
     // contract's shard_off / shard_stride on a 16-B aligned base)
     const auto store = [&](uint32_t s0) __attribute__((always_inline)) {
-      // the row stores (LDS reads + global stores) at raised issue priority
-      __builtin_amdgcn_s_setprio(1);
-      store_own<Rows>(SH, sstride, s0, nv, piece0, npieces, wave_s, lane, [] {});
-      __builtin_amdgcn_s_setprio(0);
+      store_rows<Rows>(SH, sstride, s0, nv, piece0, npieces, wave_s, lane, [] {});
     };
     // the systematic rows' store phase; the ticket thread 0 took is then
     // published (the wait for the atomic's return then counts only the stores
     // issued after it on the fast path, store_own)
     const auto store_sys = [&]() __attribute__((always_inline)) {
-      __builtin_amdgcn_s_setprio(1);
-      store_own<Rows>(SH, sstride, 0, nv, piece0, npieces, wave_s, lane, [&]() __attribute__((always_inline)) {
+      store_rows<Rows>(SH, sstride, 0, nv, piece0, npieces, wave_s, lane, [&]() __attribute__((always_inline)) {
         if (geo.publishes(tid0)) geo.publish(slot, taken, tid0);
       });
-      __builtin_amdgcn_s_setprio(0);
     };
     // the last store phase of the tile, then the next tile's State
     const auto store_last = [&](uint32_t s0) __attribute__((always_inline)) {
-      __builtin_amdgcn_s_setprio(1);
-      store_own<Rows>(SH, sstride, s0, nv, piece0, npieces, wave_s, lane,
-                 [&]() __attribute__((always_inline)) { to_state(d, nxt); });
-      __builtin_amdgcn_s_setprio(0);
+      store_rows<Rows>(SH, sstride, s0, nv, piece0, npieces, wave_s, lane,
+                       [&]() __attribute__((always_inline)) { to_state(d, nxt); });
     };
 
     // A wave none of whose 8 pieces exist (the last, partial tile of a payload:

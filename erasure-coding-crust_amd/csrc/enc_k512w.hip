@@ -1,7 +1,7 @@
 // enc_k512w.hip — encode for k = 512, n = 2048 / 4096 (n_validators 1534..3069:
 // the shapes just above a power of two), two 8-wave workgroups per CU.
 //
-// encode_k256w's model (enc_k256w.hip, its shared code in enc_w_common.hpp;
+// encode_k256w's model (enc_k256w.hip; shared code and tile schedule: enc_w_common.hpp;
 // DESIGN.md §5.1, §5.7) at k = 512: per piece (1024 payload bytes = 512
 // symbols) IFFT_512 at index 0, then FFT_512 at each coset 512 j below
 // n_validators (encodeLow, poly_encoder.hpp:217-240), radix-8 register passes
@@ -216,11 +216,12 @@ __global__ void __launch_bounds__(THREADS, 4) encode_k512w(const uint8_t *__rest
                                                            const uint8_t *__restrict__ cimg,
                                                            const uint8_t *__restrict__ eimg,
                                                            uint32_t *__restrict__ tick) {
+  // the tile schedule: the uniform batch's geometry policy (enc_w_common.hpp)
+  const UniformGeo<TILE> geo{payloads, plen, pstride, shards, slen, sstride, nv, batch, tick};
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   const uint32_t tid0 = threadIdx.x;
-  auto *slot = reinterpret_cast<__attribute__((address_space(3))) volatile uint32_t *>(uintptr_t(SLOT));
-  // this workgroup's first tile; without a counter a static grid stride
-  if (tid0 == 0) *slot = tick ? atomicAdd(tick, 1u) : blockIdx.x;
+  auto *slot = reinterpret_cast<LdsWord *>(uintptr_t(SLOT));
+  if (geo.publishes(tid0)) geo.first(slot, tid0);  // this workgroup's first tile
   {  // the compact image's F9 + subfield areas (12 KB, 768 chunks of 16 B)
     constexpr uint32_t c0 = BASE_LO / 16, n = (kCImgBytes - BASE_LO) / 16;
     const v4u a = reinterpret_cast<const v4u *>(cimg)[c0 + tid0];
@@ -231,35 +232,32 @@ __global__ void __launch_bounds__(THREADS, 4) encode_k512w(const uint8_t *__rest
   }
   __syncthreads();
 
-  const uint64_t npieces = slen / 2;
-  const uint32_t tiles_pp = uint32_t((npieces + TILE - 1) / TILE);
-  const uint32_t total = tiles_pp * batch;  // < 2^32 (launch_encode_k512w)
+  const auto pre = geo.prepare();
+  const uint32_t total = pre.total;
   const uint32_t wave_s = __builtin_amdgcn_readfirstlane(tid0 >> 6);
   // cosets 512 j, j = 1..J, below n_validators (nv <= n: launch_encode_k512w)
   const uint32_t J = uint32_t(nv - 1) / K;
-  // Dynamic schedule (enc_k256w.hip): thread 0 takes tile t + 1 at the start
-  // of tile t and publishes it in the slot after the systematic stores; every
-  // wave reads it in the last coset, after further barriers; the slot is
-  // rewritten only after the next tile's second barrier.
-  uint32_t cur = __builtin_amdgcn_readfirstlane(*slot);
+  // (the ticket protocol -- taken, published, read, rewritten: enc_w_common.hpp)
+  uint32_t cur = geo.read(slot).t;
 
-  // This lane's 4 x 16 payload bytes of tile (b, i): pieces i * TILE + 4 wave
+  // This lane's 4 x 16 payload bytes of a tile: pieces piece0 + 4 wave
   // + u, bytes 16 lane .. 16 lane + 15 of each, zero past plen; issued in the
   // previous tile's last coset, turned into the next State after its stores.
   v4u d[4];
   State nxt;
-  const auto fetch = [&](uint64_t fb, uint64_t fi) __attribute__((always_inline)) {
+  const auto fetch = [&](const UniformGeo<TILE>::Loc fl) __attribute__((always_inline)) {
     uint32_t flane = tid0;
     asm volatile("" : "+v"(flane));
     flane &= 63;
-    fetch_pieces<K>(payloads + fb * pstride, plen, npieces, fi * TILE + 4 * wave_s, 4, 0, flane, d);
+    const Fetch f = geo.fetch(pre, fl);
+    fetch_pieces<K>(f.P, f.plen, f.npieces, f.piece0 + 4 * wave_s, 4, 0, flane, d);
   };
-  if (cur < total) {
-    fetch(cur / tiles_pp, cur % tiles_pp);
+  if (geo.ticket(cur) < total) {
+    fetch(geo.loc(pre, cur));
     to_state(d, nxt);
   }
 
-  while (cur < total) {
+  while (geo.ticket(cur) < total) {
     uint32_t tid = tid0;
     asm volatile("" : "+v"(tid));
     const uint32_t lane = tid & 63, wave = tid >> 6;
@@ -270,17 +268,18 @@ __global__ void __launch_bounds__(THREADS, 4) encode_k512w(const uint8_t *__rest
     xb.a = reg0 | mswz(ulaneA(q, inst));
     xb.b = reg0 | mswz(ulaneB(q, inst));
     xb.c = reg0 | mswz(ulaneC(q, inst));
-    const uint64_t b = cur / tiles_pp, piece0 = uint64_t(cur % tiles_pp) * TILE;
-    uint32_t taken = 0;
-    if (tid0 == 0) taken = tick ? atomicAdd(tick, 1u) : cur + gridDim.x;
-    uint32_t next = 0;
-    uint8_t *SH = shards + b * uint64_t(nv) * sstride;
+    const auto at = geo.at(pre, cur);
+    const uint64_t piece0 = geo.piece0(at), npieces = geo.npieces(pre, cur), sstride = geo.sstride(cur);
+    uint32_t taken = 0;  // thread 0: the tile taken for after this one
+    if (tid0 == 0) taken = geo.next_ticket(cur);
+    uint32_t next = 0;   // every wave: that tile, read from the slot
+    uint8_t *SH = geo.rows(at);
     // every store phase of this tile takes the fast path (4 stores per lane)
     // or none does (rows 512 j < n_validators for j <= J)
     const bool fast = store_fast<Rows>(SH, sstride, 0, nv, piece0, npieces);
     const auto fetch_next = [&]() __attribute__((always_inline)) {
-      next = __builtin_amdgcn_readfirstlane(*slot);
-      fetch(next < total ? next / tiles_pp : 0, next < total ? next % tiles_pp : tiles_pp);
+      next = geo.read(slot).t;
+      fetch(geo.loc_or_none(pre, next));
     };
     const auto rsync = [&]() __attribute__((always_inline)) { lds_barrier(); };
     // coset j's extension image landed in every wave, then a barrier.  Coset
@@ -293,20 +292,17 @@ __global__ void __launch_bounds__(THREADS, 4) encode_k512w(const uint8_t *__rest
       rsync();
     };
     const auto store = [&](uint32_t s0, bool last) __attribute__((always_inline)) {
-      __builtin_amdgcn_s_setprio(1);
       if (last)
-        store_own<Rows>(SH, sstride, s0, nv, piece0, npieces, wave_s, lane,
-                  [&]() __attribute__((always_inline)) { to_state(d, nxt); });
+        store_rows<Rows>(SH, sstride, s0, nv, piece0, npieces, wave_s, lane,
+                         [&]() __attribute__((always_inline)) { to_state(d, nxt); });
       else
-        store_own<Rows>(SH, sstride, s0, nv, piece0, npieces, wave_s, lane, [] {});
-      __builtin_amdgcn_s_setprio(0);
+        store_rows<Rows>(SH, sstride, s0, nv, piece0, npieces, wave_s, lane, [] {});
     };
+    // the systematic rows' store phase, then the ticket thread 0 took is published
     const auto store_sys = [&]() __attribute__((always_inline)) {
-      __builtin_amdgcn_s_setprio(1);
-      store_own<Rows>(SH, sstride, 0, nv, piece0, npieces, wave_s, lane, [&]() __attribute__((always_inline)) {
-        if (tid0 == 0) *slot = taken;
+      store_rows<Rows>(SH, sstride, 0, nv, piece0, npieces, wave_s, lane, [&]() __attribute__((always_inline)) {
+        if (geo.publishes(tid0)) geo.publish(slot, taken, tid0);
       });
-      __builtin_amdgcn_s_setprio(0);
     };
     // coset 1's extension image, after the systematic stores (their tile-slot
     // write waits for thread 0's ticket: a DMA issued before them would be
@@ -317,101 +313,94 @@ __global__ void __launch_bounds__(THREADS, 4) encode_k512w(const uint8_t *__rest
       dma_ext(eimg, 1, wave_s, lane);
     };
 
-    // a wave none of whose 4 pieces exist (the payload's last, partial tile)
-    // takes part only in the barriers, the DMAs and the row stores (uniform)
-    if (piece0 + 4 * wave_s >= npieces) {
-      rsync();  // tile start
+    // ---- the tile: its barriers, LDS-DMA issues, counted waits and store phases,
+    // written once.  A wave with pieces (LIVE) also stages and transforms; one
+    // with none (the payload's last, partial tile) runs the same sequence bare.
+    const uint32_t baseA = 8 * lane, baseB = (inst << 8) | posB(q, 0);  // lane parts of the positions
+    const auto run = [&](auto live) __attribute__((always_inline)) {
+      constexpr bool LIVE = decltype(live)::value;
+      [[maybe_unused]] State s, coef;
+      if constexpr (LIVE) s = nxt;
+      // ---- systematic shards 0..511 = the data symbols (poly_encoder.hpp:239)
+      rsync();  // tile start: the other waves are done reading the regions (last tile)
+      if constexpr (LIVE) stage_own(s, lane, wave);
       rsync();  // systematic rows staged
       store_sys_dma();
-      rsync();  // after IFFT pass A
+      if constexpr (LIVE) {
+        __builtin_amdgcn_sched_barrier(0);
+        {  // into tower coordinates
+          const TowerK tk = tower_k();
+#pragma unroll
+          for (int r = 0; r < 8; ++r) s.l[r] = tower_lo(s.l[r], s.h[r], tk);
+        }
+        // ---- IFFT_512 (index 0): passes A (bits 0-2), B (3-5), C' (6-8)
+        ipassA(s, baseA, hi);
+      }
+      rsync();  // after IFFT pass A: systematic rows read out of the regions
+      if constexpr (LIVE) {
+        xchg<LA, LB>(s, xb);
+        ipass<3>(s, baseB);
+        xchg<LB, LC>(s, xb);
+        swap_c(s);
+        ipassC9(s);
+        coef = s;
+      }
+
+      // ---- FFT_512 at each coset 512 j (encodeLow, poly_encoder.hpp:229-237).
+      // Kinds by coset (x = (pos + off) >> (m + 1), ec_kernels.hpp): stage 3
+      // subfield for j <= 3, F9 above; stage 2 subfield (j = 1), F9 (2, 3),
+      // extension (4..7); stage 1 F9 (j = 1), extension above; stage 0
+      // extension; stages 4-8 subfield.
+      [[maybe_unused]] const auto coset = [&](auto k3, auto k2, auto k1, const uint32_t j)
+                                              __attribute__((always_inline)) {
+        using K3 = decltype(k3);
+        using K2 = decltype(k2);
+        using K1 = decltype(k1);
+        const uint32_t off = K * j;
+        // lane bases laundered per coset: the table addresses derived from them
+        // are formed in the passes, not hoisted out of the coset loop (spilled)
+        uint32_t bA = baseA, bB = baseB;
+        asm volatile("" : "+v"(bA), "+v"(bB));
+#pragma unroll
+        for (int r = 0; r < 8; ++r) asm volatile("" : "+v"(coef.l[r]), "+v"(coef.h[r]));
+        fpassC9(s, coef, off);
+        swap_c(s);
+        ext_ready(j);  // + the previous coset's rows read out of the regions
+        xchg<LC, LB>(s, xb);
+        fpass<3, SubTab, SubTab, K3>(s, bB, off);
+        xchg<LB, LA>(s, xb);
+        fpass<0, K2, K1, EG<0>>(s, bA, off);
+        {  // back to symbol coordinates
+          const TowerK tk = tower_k();
+#pragma unroll
+          for (int r = 0; r < 8; ++r) s.l[r] = tower_lo(s.l[r], s.h[r], tk);
+        }
+        stage_own(s, lane, wave);
+      };
+      // the cosets in a loop (three bodies, by table kinds); the last one leaves
+      // it, so the next tile's payload (d, nxt) is live in that one only
       for (uint32_t j = 1;; ++j) {
-        ext_ready(j);
+        if constexpr (LIVE) {
+          if (j == 1) coset(SubTab(), SubTab(), F9Tab(), j);
+          else if (j <= 3) coset(SubTab(), F9Tab(), EG<1>(), j);
+          else coset(F9Tab(), EG<2>(), EG<1>(), j);
+        } else {
+          ext_ready(j);  // the coset body's wait and barrier
+        }
         if (j == J) {
-          fetch_next();
-          rsync();  // rows staged
+          fetch_next();  // coef and s are dead here
+          rsync();       // rows staged
           store(K * j, true);
           break;
         }
-        rsync();  // rows staged
+        rsync();  // rows staged; every wave is past this coset's tables
         dma_ext(eimg, j + 1, wave_s, lane);
         store(K * j, false);
         __builtin_amdgcn_sched_barrier(0);
       }
-      cur = next;
-      continue;
-    }
-
-    State s = nxt;
-    // ---- systematic shards 0..511 = the data symbols (poly_encoder.hpp:239)
-    rsync();  // the other waves are done reading the regions (last tile)
-    stage_own(s, lane, wave);
-    rsync();
-    store_sys_dma();
-    __builtin_amdgcn_sched_barrier(0);
-    {  // into tower coordinates
-      const TowerK tk = tower_k();
-#pragma unroll
-      for (int r = 0; r < 8; ++r) s.l[r] = tower_lo(s.l[r], s.h[r], tk);
-    }
-
-    // ---- IFFT_512 (index 0): passes A (bits 0-2), B (3-5), C' (6-8)
-    const uint32_t baseA = 8 * lane, baseB = (inst << 8) | posB(q, 0);
-    ipassA(s, baseA, hi);
-    rsync();  // systematic rows read out of the regions
-    xchg<LA, LB>(s, xb);
-    ipass<3>(s, baseB);
-    xchg<LB, LC>(s, xb);
-    swap_c(s);
-    ipassC9(s);
-    State coef = s;
-
-    // ---- FFT_512 at each coset 512 j (encodeLow, poly_encoder.hpp:229-237).
-    // Kinds by coset (x = (pos + off) >> (m + 1), ec_kernels.hpp): stage 3
-    // subfield for j <= 3, F9 above; stage 2 subfield (j = 1), F9 (2, 3),
-    // extension (4..7); stage 1 F9 (j = 1), extension above; stage 0
-    // extension; stages 4-8 subfield.
-    const auto coset = [&](auto k3, auto k2, auto k1, const uint32_t j) __attribute__((always_inline)) {
-      using K3 = decltype(k3);
-      using K2 = decltype(k2);
-      using K1 = decltype(k1);
-      const uint32_t off = K * j;
-      // lane bases laundered per coset: the table addresses derived from them
-      // are formed in the passes, not hoisted out of the coset loop (spilled)
-      uint32_t bA = baseA, bB = baseB;
-      asm volatile("" : "+v"(bA), "+v"(bB));
-#pragma unroll
-      for (int r = 0; r < 8; ++r) asm volatile("" : "+v"(coef.l[r]), "+v"(coef.h[r]));
-      fpassC9(s, coef, off);
-      swap_c(s);
-      ext_ready(j);  // + the previous coset's rows read out of the regions
-      xchg<LC, LB>(s, xb);
-      fpass<3, SubTab, SubTab, K3>(s, bB, off);
-      xchg<LB, LA>(s, xb);
-      fpass<0, K2, K1, EG<0>>(s, bA, off);
-      {  // back to symbol coordinates
-        const TowerK tk = tower_k();
-#pragma unroll
-        for (int r = 0; r < 8; ++r) s.l[r] = tower_lo(s.l[r], s.h[r], tk);
-      }
-      stage_own(s, lane, wave);
     };
-    // the cosets in a loop (three bodies, by table kinds); the last one leaves
-    // it, so the next tile's payload (d, nxt) is live in that one only
-    for (uint32_t j = 1;; ++j) {
-      if (j == 1) coset(SubTab(), SubTab(), F9Tab(), j);
-      else if (j <= 3) coset(SubTab(), F9Tab(), EG<1>(), j);
-      else coset(F9Tab(), EG<2>(), EG<1>(), j);
-      if (j == J) {
-        fetch_next();  // coef and s are dead here
-        rsync();       // rows staged
-        store(K * j, true);
-        break;
-      }
-      rsync();  // rows staged; every wave is past this coset's tables
-      dma_ext(eimg, j + 1, wave_s, lane);
-      store(K * j, false);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    if (piece0 + 4 * wave_s >= npieces) run(std::false_type());  // (wave-uniform)
+    else run(std::true_type());
     cur = next;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no LDS-DMA outlives the workgroup

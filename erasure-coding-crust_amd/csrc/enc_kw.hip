@@ -2,7 +2,7 @@
 // 46..765, the Polkadot validator counts of today among them) and k = 256 at
 // n = 2048 (n_validators 1025..1533), two 8-wave workgroups per CU.
 //
-// encode_k256w's model (enc_k256w.hip, its shared code in enc_w_common.hpp;
+// encode_k256w's model (enc_k256w.hip; shared code and tile schedule: enc_w_common.hpp;
 // DESIGN.md §5.1, §5.7): per piece (2 k payload bytes = k symbols) IFFT_k at index 0, then FFT_k at each coset k j
 // below n_validators (encodeLow, poly_encoder.hpp:217-240), radix-8 register
 // passes in tower coordinates, wave-private LDS exchanges.  A wave holds NG =
@@ -181,37 +181,41 @@ __global__ void __launch_bounds__(THREADS, 4) encode_kw(const uint8_t *__restric
                                                         uint32_t *__restrict__ tick) {
   using G = Geo<M>;
   constexpr uint32_t K = G::K;
+  // the tile schedule: the uniform batch's geometry policy (enc_w_common.hpp)
+  using UGeo = UniformGeo<G::TILE>;
+  const UGeo geo{payloads, plen, pstride, shards, slen, sstride, nv, batch, tick};
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   const uint32_t tid0 = threadIdx.x;
-  auto *slot = reinterpret_cast<__attribute__((address_space(3))) volatile uint32_t *>(uintptr_t(SLOT));
-  if (tid0 == 0) *slot = tick ? atomicAdd(tick, 1u) : blockIdx.x;
+  auto *slot = reinterpret_cast<LdsWord *>(uintptr_t(SLOT));
+  if (geo.publishes(tid0)) geo.first(slot, tid0);  // this workgroup's first tile
   copy_cimg(lds, cimg, tid0);
   __syncthreads();
 
-  const uint64_t npieces = slen / 2;
-  const uint32_t tiles_pp = uint32_t((npieces + G::TILE - 1) / G::TILE);
-  const uint32_t total = tiles_pp * batch;  // < 2^32 (launch_encode_kw)
+  const auto pre = geo.prepare();
+  const uint32_t total = pre.total;
   const uint32_t wave_s = __builtin_amdgcn_readfirstlane(tid0 >> 6);
   const uint32_t J = uint32_t(nv - 1) / K;  // cosets k j, j = 1..J <= 7 (nv <= n <= 8 k)
-  uint32_t cur = __builtin_amdgcn_readfirstlane(*slot);
+  // (the ticket protocol -- taken, published, read, rewritten: enc_w_common.hpp)
+  uint32_t cur = geo.read(slot).t;
 
-  // This lane's 4 x 16 payload bytes of tile (b, i): pieces i * TILE + WP wave
+  // This lane's 4 x 16 payload bytes of a tile: pieces piece0 + WP wave
   // + 4 g + u (g = lane >> (M - 3)), bytes 16 q .. 16 q + 15 of each (q = lane
   // & QM), zero past plen; issued in the previous tile's last coset.
   v4u d[4];
   State nxt;
-  const auto fetch = [&](uint64_t fb, uint64_t fi) __attribute__((always_inline)) {
+  const auto fetch = [&](const typename UGeo::Loc fl) __attribute__((always_inline)) {
     uint32_t ftid = tid0;
     asm volatile("" : "+v"(ftid));
     const uint32_t lane = ftid & 63, g = lane >> (M - 3), q = lane & G::QM;
-    fetch_pieces<K>(payloads + fb * pstride, plen, npieces, fi * G::TILE + G::WP * wave_s, G::WP, g, q, d);
+    const Fetch f = geo.fetch(pre, fl);
+    fetch_pieces<K>(f.P, f.plen, f.npieces, f.piece0 + G::WP * wave_s, G::WP, g, q, d);
   };
-  if (cur < total) {
-    fetch(cur / tiles_pp, cur % tiles_pp);
+  if (geo.ticket(cur) < total) {
+    fetch(geo.loc(pre, cur));
     to_state(d, nxt);
   }
 
-  while (cur < total) {
+  while (geo.ticket(cur) < total) {
     uint32_t tid = tid0;
     asm volatile("" : "+v"(tid));
     const uint32_t lane = tid & 63, wave = tid >> 6;
@@ -223,11 +227,12 @@ __global__ void __launch_bounds__(THREADS, 4) encode_kw(const uint8_t *__restric
     xb.a = reg0 | mswz(ulaneA(q5, i0));
     xb.b = reg0 | mswz(ulaneB(q5, i0));
     xb.c = reg0 | mswz(ulaneC(q5, i0));
-    const uint64_t b = cur / tiles_pp, piece0 = uint64_t(cur % tiles_pp) * G::TILE;
-    uint32_t taken = 0;
-    if (tid0 == 0) taken = tick ? atomicAdd(tick, 1u) : cur + gridDim.x;
-    uint32_t next = 0;
-    uint8_t *SH = shards + b * uint64_t(nv) * sstride;
+    const auto at = geo.at(pre, cur);
+    const uint64_t piece0 = geo.piece0(at), npieces = geo.npieces(pre, cur), sstride = geo.sstride(cur);
+    uint32_t taken = 0;  // thread 0: the tile taken for after this one
+    if (tid0 == 0) taken = geo.next_ticket(cur);
+    uint32_t next = 0;   // every wave: that tile, read from the slot
+    uint8_t *SH = geo.rows(at);
     // every store phase of this tile but possibly the last coset's takes the
     // fast path (4 stores per lane), or none does
     [[maybe_unused]] const bool fast = store_fast<Rows<M>>(SH, sstride, 0, nv, piece0, npieces);
@@ -239,25 +244,22 @@ __global__ void __launch_bounds__(THREADS, 4) encode_kw(const uint8_t *__restric
         lds_dma16(EXT8 + 1024 * i, src + 1024 * i);
     };
     const auto fetch_next = [&]() __attribute__((always_inline)) {
-      next = __builtin_amdgcn_readfirstlane(*slot);
-      fetch(next < total ? next / tiles_pp : 0, next < total ? next % tiles_pp : tiles_pp);
+      next = geo.read(slot).t;
+      fetch(geo.loc_or_none(pre, next));
     };
     const auto rsync = [&]() __attribute__((always_inline)) { lds_barrier(); };
     const auto store = [&](uint32_t s0, bool last) __attribute__((always_inline)) {
-      __builtin_amdgcn_s_setprio(1);
       if (last)
-        store_own<Rows<M>>(SH, sstride, s0, nv, piece0, npieces, wave_s, lane,
-                     [&]() __attribute__((always_inline)) { to_state(d, nxt); });
+        store_rows<Rows<M>>(SH, sstride, s0, nv, piece0, npieces, wave_s, lane,
+                            [&]() __attribute__((always_inline)) { to_state(d, nxt); });
       else
-        store_own<Rows<M>>(SH, sstride, s0, nv, piece0, npieces, wave_s, lane, [] {});
-      __builtin_amdgcn_s_setprio(0);
+        store_rows<Rows<M>>(SH, sstride, s0, nv, piece0, npieces, wave_s, lane, [] {});
     };
+    // the systematic rows' store phase, then the ticket thread 0 took is published
     const auto store_sys = [&]() __attribute__((always_inline)) {
-      __builtin_amdgcn_s_setprio(1);
-      store_own<Rows<M>>(SH, sstride, 0, nv, piece0, npieces, wave_s, lane, [&]() __attribute__((always_inline)) {
-        if (tid0 == 0) *slot = taken;
+      store_rows<Rows<M>>(SH, sstride, 0, nv, piece0, npieces, wave_s, lane, [&]() __attribute__((always_inline)) {
+        if (geo.publishes(tid0)) geo.publish(slot, taken, tid0);
       });
-      __builtin_amdgcn_s_setprio(0);
     };
 
     // a wave none of whose pieces exist (the payload's last, partial tile)

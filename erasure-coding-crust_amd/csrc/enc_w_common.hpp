@@ -3,9 +3,10 @@
 // §5.7): 8-wave workgroups on the compact table image (cimg.hpp), radix-8
 // register passes in tower coordinates, wave-private LDS exchanges
 // (enc_k256_common.hpp), the payload fetch of a lane, the row stores out of
-// the waves' own regions and the launchers' tail.  Each kernel keeps its tile
-// loop, its idle-wave path, its coset sequencing, its LDS map and its staging
-// swizzle (soff*).
+// the waves' own regions, the tile schedule (the geometry policy's contract,
+// the ticket protocol, the uniform batch's policy UniformGeo) and the
+// launchers' tail.  Each kernel keeps its tile loop with its barrier sequence,
+// its passes and table kinds, its LDS map and its staging swizzle (soff*).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -311,6 +312,126 @@ __device__ __forceinline__ void store_own(uint8_t *SH, uint64_t sstride, uint32_
   then();
   asm volatile("; store_own slow path end" ::: "memory");
 }
+
+// a store phase: the row stores (LDS reads + global stores) at raised issue priority
+template <typename G, typename Then>
+__device__ __forceinline__ void store_rows(uint8_t *SH, uint64_t sstride, uint32_t s0, int nv, uint64_t piece0,
+                                           uint64_t npieces, uint32_t wave, uint32_t lane, Then &&then) {
+  __builtin_amdgcn_s_setprio(1);
+  store_own<G>(SH, sstride, s0, nv, piece0, npieces, wave, lane, then);
+  __builtin_amdgcn_s_setprio(0);
+}
+
+// ---- the tile schedule.  The kernels are persistent: a workgroup works on
+// tile tickets until one is past the launch's last tile.  A tile loop is
+// written against a geometry policy that says, for a ticket, which payload
+// bytes, shard rows, piece count and pitch the tile works on, and how the
+// ticket travels from the thread that takes it to the other waves; the
+// transforms, the staging, the row stores and the order of barriers do not
+// depend on it.  UniformGeo below: the uniform batch (encode_k256w, encode_kw,
+// encode_k512w); the ragged batch: enc_k256w_ragged.hip.
+//
+// A geometry policy Geo provides (all values wave-uniform):
+//   Tile, ticket(T)      what a wave keeps of a ticket from reading it to the
+//                        end of its tile; ticket(T) < Pre::total: a tile of
+//                        the launch
+//   SLOT_BYTES           LDS bytes at the kernel's SLOT the tickets are published in
+//   Pre, prepare()       worked out once per launch; total: the launch's tiles
+//   publishes(tid0)      the threads that take part in publishing a ticket
+//                        (thread 0, or all of wave 0); the call sites are
+//                        reached by whole waves, wave 0 always among them
+//   first(slot, tid0)    those threads: take and publish the first ticket
+//   next_ticket(T)       thread 0: the ticket after tile T's
+//   publish(slot, ticket, tid0)  those threads: resolve and store thread 0's ticket
+//   read(slot).t         the published Tile (after a barrier)
+//   Loc, loc(pre, T)     where a valid tile's payload bytes are
+//   loc_or_none(pre, T)  the same for a tile that may be past the end: then a
+//                        place for which the fetch loads nothing
+//   fetch(pre, Loc)      the payload fetch's geometry (Fetch)
+//   At, at(pre, T), piece0(At), rows(At), npieces(pre, T), sstride(T)
+//                        geometry of a valid tile's transforms and stores
+//
+// The ticket protocol.  Tiles come from the launch's counter (zeroed before the
+// launch), so the two workgroups of a CU, which the issue arbiter serves at
+// unequal rates, finish together: with a static grid-stride split the faster
+// one ended up to 2.8 ms before the slower one of a 7 ms launch
+// (scripts/variants/clk_run.py).  A ticket is
+//  * taken by thread 0 at the start of the tile before its own (next_ticket:
+//    the atomic's latency hides behind that tile);
+//  * published in the LDS slot after that tile's systematic stores (the store
+//    phase's `then`: the wait for the atomic's return counts only the stores
+//    issued after it on the fast path, store_own);
+//  * read by every wave in that tile's last coset (fetch_next), at least one
+//    barrier later (the one after IFFT pass A);
+//  * rewritten only after the next tile's systematic stores, past that tile's
+//    start barrier, by which every wave has read it.
+// The first ticket is published before the kernel's first __syncthreads.
+//
+// what the payload fetch of a tile needs: the item's payload, its length in
+// bytes and pieces, the tile's first piece
+struct Fetch {
+  const uint8_t *P;
+  uint64_t plen, npieces, piece0;
+};
+
+// The uniform batch in tiles of TILE pieces: payload b at b * pstride, its
+// rows at b * nv * sstride, every payload plen bytes: ticket cur is tile
+// cur % tiles_pp of payload cur / tiles_pp.  Without a counter (no scratch) a
+// static grid stride (slower: the two workgroups of a CU drift apart).
+template <int TILE>
+struct UniformGeo {
+  const uint8_t *payloads;
+  uint64_t plen_, pstride;
+  uint8_t *shards;
+  uint64_t slen, sstride_;
+  int nv;
+  uint32_t batch;
+  uint32_t *tick;
+  using Tile = uint32_t;  // the ticket itself
+  static constexpr uint32_t SLOT_BYTES = 16;
+  struct Pre {  // per launch: pieces and tiles per payload, tiles of the launch
+    uint64_t npieces;
+    uint32_t tiles_pp, total;
+  };
+  __device__ __forceinline__ Pre prepare() const {
+    const uint64_t npieces = slen / 2;
+    const uint32_t tiles_pp = uint32_t((npieces + TILE - 1) / TILE);
+    return {npieces, tiles_pp, tiles_pp * batch};  // < 2^32 (launch_w)
+  }
+  __device__ __forceinline__ bool publishes(uint32_t tid0) const { return tid0 == 0; }
+  __device__ __forceinline__ void first(LdsWord *slot, uint32_t) const {
+    *slot = tick ? atomicAdd(tick, 1u) : blockIdx.x;
+  }
+  __device__ __forceinline__ uint32_t next_ticket(Tile c) const {
+    return tick ? atomicAdd(tick, 1u) : c + gridDim.x;
+  }
+  __device__ __forceinline__ void publish(LdsWord *slot, uint32_t ticket, uint32_t) const { *slot = ticket; }
+  struct Read {
+    Tile t;
+  };
+  __device__ __forceinline__ Read read(LdsWord *slot) const { return {uint32_t(__builtin_amdgcn_readfirstlane(*slot))}; }
+  __device__ __forceinline__ uint32_t ticket(Tile c) const { return c; }
+  struct Loc {
+    uint64_t b, i;  // payload, tile in the payload
+  };
+  __device__ __forceinline__ Loc loc(const Pre &p, Tile c) const { return {c / p.tiles_pp, c % p.tiles_pp}; }
+  // past the end: the zero path, no loads
+  __device__ __forceinline__ Loc loc_or_none(const Pre &p, Tile c) const {
+    return {c < p.total ? uint64_t(c / p.tiles_pp) : uint64_t(0),
+            uint64_t(c < p.total ? c % p.tiles_pp : p.tiles_pp)};
+  }
+  __device__ __forceinline__ Fetch fetch(const Pre &p, Loc l) const {
+    return {payloads + l.b * pstride, plen_, p.npieces, l.i * TILE};
+  }
+  struct At {
+    uint64_t b, piece0;  // a valid tile's payload and first piece
+  };
+  __device__ __forceinline__ At at(const Pre &p, Tile c) const { return {c / p.tiles_pp, uint64_t(c % p.tiles_pp) * TILE}; }
+  __device__ __forceinline__ uint64_t piece0(At a) const { return a.piece0; }
+  __device__ __forceinline__ uint64_t npieces(const Pre &p, Tile) const { return p.npieces; }
+  __device__ __forceinline__ uint64_t sstride(Tile) const { return sstride_; }
+  __device__ __forceinline__ uint8_t *rows(At a) const { return shards + a.b * uint64_t(nv) * sstride_; }
+};
 
 }  // namespace
 

@@ -145,7 +145,8 @@ for k in kinds:
         com = rep(com, "      __builtin_nontemporal_store(val, reinterpret_cast<v4u *>(dst + it * dstep));  // written once\n",
                   "      *reinterpret_cast<v4u *>(dst + it * dstep) = val;\n")
     elif k == "noprio":
-        enc = enc.replace("__builtin_amdgcn_s_setprio(1);", "").replace("__builtin_amdgcn_s_setprio(0);", "")
+        # the store phases' one wrapper (enc_w_common.hpp store_rows)
+        com = rep(rep(com, "  __builtin_amdgcn_s_setprio(1);\n", ""), "  __builtin_amdgcn_s_setprio(0);\n", "")
     elif k == "clk":
         enc = rep(enc, "namespace ecamd {\nnamespace {", "namespace ecamd {\n__device__ unsigned long long g_stamp[16];\nnamespace {")
         enc = rep(enc, "  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];\n",

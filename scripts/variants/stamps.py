@@ -85,9 +85,11 @@ elif kind == "encw":
     s = rep(s, "  __syncthreads();\n\n  const auto pre = geo.prepare();", "  __syncthreads();\n" + STAMP + "\n  const auto pre = geo.prepare();")
     s = rep(s, "    const auto rsync = [&]() __attribute__((always_inline)) { lds_barrier(); };",
             "    const auto rsync = [&]() __attribute__((always_inline)) { STAMP(3); lds_barrier(); STAMP(1); };")
-    # both store lambdas (store, store_last)
-    s = rep(s, "      __builtin_amdgcn_s_setprio(1);\n", "      STAMP(3);\n      __builtin_amdgcn_s_setprio(1);\n", 3)
-    s = rep(s, "      __builtin_amdgcn_s_setprio(0);\n    };", "      __builtin_amdgcn_s_setprio(0);\n      STAMP(2);\n    };", 3)
+    # the three store lambdas (store, store_sys, store_last): around their
+    # store phase (enc_w_common.hpp store_rows)
+    s = rep(s, "      store_rows<Rows>(", "      STAMP(3);\n      store_rows<Rows>(", 3)
+    for end in ("lane, [] {});\n    };", "      });\n    };", "{ to_state(d, nxt); });\n    };"):
+        s = rep(s, end, end[:-len("    };")] + "      STAMP(2);\n    };")
     s = rep(s, "    // ---- systematic shards 0..255 = the data symbols (poly_encoder.hpp:239)\n",
             "    STAMP(0);\n    // ---- systematic shards 0..255 = the data symbols (poly_encoder.hpp:239)\n")
     s = rep(s, "  }\n}\n}\n\nhipError_t launch_encode_k256w", "  }\n" + FLUSH + "}\n}\n\nhipError_t launch_encode_k256w")
