@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <optional>
 #include <string>
 #include <vector>
@@ -541,6 +542,76 @@ NPRSResult reconstruct_batch(unsigned long nv, const ReconCall &c, hipStream_t s
   return result(NPRS_RESULT_OK);
 }
 
+// ---- the masked encode and the repair (ec_amd.h "repair").  Like the ragged
+// calls they always need scratch and check what the host can see -- NULL
+// buffers, the encode's / reconstruct's own predicate, the caller's workspace
+// -- before the device is touched: nothing is launched on a refusal.
+bool refuse_null(const char *what, std::initializer_list<const void *> bufs) {
+  for (const void *b : bufs)
+    if (!b) {
+      set_error(std::string("erasure_coding_crust(amd): ") + what + ": a NULL buffer");
+      return true;
+    }
+  return false;
+}
+
+NPRSResult encode_missing_batch(unsigned long nv, const MissingCall &c, hipStream_t s, const Workspace *ws) {
+  CodeParams p;
+  NPRSResult r = params_or_error(nv, &p);
+  if (r.tag != NPRS_RESULT_OK) return r;
+  if (refuse_null("encode_missing_batch", {c.enc.payloads, c.enc.shards, c.present}))
+    return result(NPRS_RESULT_BAD_PAYLOAD);
+  if (const NPRSResult_Tag t = encode_call_tag(p, c.enc); t != NPRS_RESULT_OK) return result(t);
+  if (c.enc.batch == 0) return result(NPRS_RESULT_OK);  // an empty call, as the encode's
+  const size_t need = encode_missing_scratch_bytes(p, c.enc.plen, c.enc.batch);
+  if (ws && !workspace_fits(*ws, need)) {
+    workspace_error(*ws, need, "masked encode needs (ECCR_AMD_encode_missing_workspace_bytes)");
+    return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
+  }
+  DeviceState *d = device_state();
+  if (!d) return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
+  BatchScratch sc(d, need, s, ws);
+  if (!sc.ok || !hip_check(launch_encode_missing(p, device_tables(d), c, sc.p, s), "masked encode launch"))
+    return result(NPRS_RESULT_UNKNOWN_CODE_PARAM);
+  return result(NPRS_RESULT_OK);
+}
+
+// the encode stage of a repair: the reconstruct's output is its payloads
+// (shard_len * k bytes each, pitch out_stride), its rows the reconstruct's input
+MissingCall repair_encode_call(const CodeParams &p, const ReconCall &c) {
+  return {{c.out, c.slen * p.k, c.ostride, c.batch, const_cast<uint8_t *>(c.shards), c.sstride}, c.present, c.pattern};
+}
+// one workspace for both stages: they are ordered on the stream, and the
+// reconstruct's scratch is dead when the masked encode's plan is written
+size_t repair_scratch_bytes(const CodeParams &p, size_t slen, size_t batch) {
+  const size_t need =
+      std::max(reconstruct_scratch_bytes(p, slen, batch), encode_missing_scratch_bytes(p, slen * p.k, batch));
+  return (need + 255) / 256 * 256;
+}
+
+NPRSResult repair_batch(unsigned long nv, const ReconCall &c, hipStream_t s, const Workspace *ws) {
+  CodeParams p;
+  NPRSResult r = params_or_error(nv, &p);
+  if (r.tag != NPRS_RESULT_OK) return r;
+  if (refuse_null("repair_batch", {c.shards, c.present, c.err_log, c.out})) return result(NPRS_RESULT_BAD_PAYLOAD);
+  if (const NPRSResult_Tag t = recon_call_tag(p, c); t != NPRS_RESULT_OK) return result(t);
+  const MissingCall mc = repair_encode_call(p, c);
+  if (const NPRSResult_Tag t = encode_call_tag(p, mc.enc); t != NPRS_RESULT_OK) return result(t);  // shard_len 0
+  if (c.batch == 0) return result(NPRS_RESULT_OK);
+  const size_t need = repair_scratch_bytes(p, c.slen, c.batch);
+  if (ws && !workspace_fits(*ws, need)) {
+    workspace_error(*ws, need, "repair needs (ECCR_AMD_repair_workspace_bytes)");
+    return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
+  }
+  DeviceState *d = device_state();
+  if (!d) return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
+  BatchScratch sc(d, need, s, ws);
+  if (!sc.ok || !hip_check(launch_reconstruct(p, device_tables(d), c, sc.p, s), "repair: reconstruct launch") ||
+      !hip_check(launch_encode_missing(p, device_tables(d), mc, sc.p, s), "repair: masked encode launch"))
+    return result(NPRS_RESULT_UNKNOWN_RECONSTRUCTION);
+  return result(NPRS_RESULT_OK);
+}
+
 // The scratch is systematic_w's tile counter only: a workspace that does not
 // fit (NULL, short or misaligned) runs the static schedule.
 NPRSResult systematic_batch(unsigned long nv, SysCall c, hipStream_t s, const Workspace *ws) {
@@ -830,6 +901,61 @@ const char *ECCR_AMD_reconstruct_kernel(unsigned long nv, const uint8_t *d_shard
 }
 
 int ECCR_AMD_reconstruct_n1024x_waves(unsigned long slen) { return n1024x_waves(slen); }
+
+NPRSResult ECCR_AMD_encode_missing_batch(unsigned long nv, const uint8_t *d_payloads, unsigned long plen,
+                                         unsigned long pstride, unsigned long batch, uint8_t *d_shards,
+                                         unsigned long sstride, const uint8_t *d_present,
+                                         const uint32_t *d_pattern, void *stream) {
+  return encode_missing_batch(nv, {{d_payloads, plen, pstride, batch, d_shards, sstride}, d_present, d_pattern},
+                              static_cast<hipStream_t>(stream), nullptr);
+}
+
+NPRSResult ECCR_AMD_encode_missing_batch_ws(unsigned long nv, const uint8_t *d_payloads, unsigned long plen,
+                                            unsigned long pstride, unsigned long batch, uint8_t *d_shards,
+                                            unsigned long sstride, const uint8_t *d_present,
+                                            const uint32_t *d_pattern, void *d_workspace,
+                                            unsigned long workspace_bytes, void *stream) {
+  const Workspace ws{d_workspace, workspace_bytes};
+  return encode_missing_batch(nv, {{d_payloads, plen, pstride, batch, d_shards, sstride}, d_present, d_pattern},
+                              static_cast<hipStream_t>(stream), &ws);
+}
+
+unsigned long ECCR_AMD_encode_missing_workspace_bytes(unsigned long nv, unsigned long plen, unsigned long batch) {
+  CodeParams p;
+  if (code_params(nv, &p) != ParamError::kOk || plen == 0 || batch == 0) return 0;
+  return encode_missing_scratch_bytes(p, plen, batch);
+}
+
+const char *ECCR_AMD_encode_missing_kernel(unsigned long nv, const uint8_t *d_payloads, unsigned long plen,
+                                           unsigned long pstride, unsigned long batch, const uint8_t *d_shards,
+                                           unsigned long sstride) {
+  CodeParams p;
+  const MissingCall c{{d_payloads, plen, pstride, batch, const_cast<uint8_t *>(d_shards), sstride}, nullptr, nullptr};
+  if (code_params(nv, &p) != ParamError::kOk || encode_call_tag(p, c.enc) != NPRS_RESULT_OK) return nullptr;
+  return kernel_name(choose_encode_missing(p, c));
+}
+
+NPRSResult ECCR_AMD_repair_batch(unsigned long nv, uint8_t *d_shards, unsigned long slen, unsigned long sstride,
+                                 const uint8_t *d_present, const uint16_t *d_err_log, const uint32_t *d_pattern,
+                                 unsigned long batch, uint8_t *d_out, unsigned long ostride, void *stream) {
+  return repair_batch(nv, {d_shards, slen, sstride, d_present, d_err_log, d_pattern, batch, d_out, ostride},
+                      static_cast<hipStream_t>(stream), nullptr);
+}
+
+NPRSResult ECCR_AMD_repair_batch_ws(unsigned long nv, uint8_t *d_shards, unsigned long slen, unsigned long sstride,
+                                    const uint8_t *d_present, const uint16_t *d_err_log, const uint32_t *d_pattern,
+                                    unsigned long batch, uint8_t *d_out, unsigned long ostride, void *d_workspace,
+                                    unsigned long workspace_bytes, void *stream) {
+  const Workspace ws{d_workspace, workspace_bytes};
+  return repair_batch(nv, {d_shards, slen, sstride, d_present, d_err_log, d_pattern, batch, d_out, ostride},
+                      static_cast<hipStream_t>(stream), &ws);
+}
+
+unsigned long ECCR_AMD_repair_workspace_bytes(unsigned long nv, unsigned long slen, unsigned long batch) {
+  CodeParams p;
+  if (code_params(nv, &p) != ParamError::kOk || slen == 0 || slen % 2 != 0 || batch == 0) return 0;
+  return repair_scratch_bytes(p, slen, batch);
+}
 
 NPRSResult ECCR_AMD_locator_cache_stats(unsigned long *hits, unsigned long *misses) {
   DeviceState *d = device_state();

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "ec_device.hpp"
 #include "ec_kernels.hpp"
@@ -159,6 +160,7 @@ struct EncItemG {
 // the uniform batch: item b at b * pitch, every item as long as the others
 struct UniformEncG {
   uint64_t plen, pstride, slen, sstride;
+  static constexpr bool MASKED = false;
   struct Pre {
     uint64_t npieces;  // per launch: pieces per payload
   };
@@ -168,6 +170,33 @@ struct UniformEncG {
     return {payloads + uint64_t(b) * pstride, shards + uint64_t(b) * nv * sstride, plen, p.npieces, sstride, true};
   }
 };
+// the masked encode (encode_g_missing): the uniform batch, and payload b's
+// present row (n bytes a row; row pattern[b] with a pattern array)
+struct MissingEncG {
+  UniformEncG u;
+  const uint8_t *present;
+  const uint32_t *pattern;
+  uint32_t n;
+  static constexpr bool MASKED = true;
+  using Pre = UniformEncG::Pre;
+  __device__ __forceinline__ Pre prepare() const { return u.prepare(); }
+  __device__ __forceinline__ EncItemG item(const Pre &p, const uint8_t *payloads, uint8_t *shards, uint32_t b,
+                                           int nv) const {
+    return u.item(p, payloads, shards, b, nv);
+  }
+  __device__ __forceinline__ const uint8_t *present_row(uint32_t b) const {
+    return present + uint64_t(pattern ? pattern[b] : b) * n;
+  }
+};
+// a MASKED policy's present row of payload b (a form that compiles for every
+// policy: the body is a fragment inside non-template kernels)
+template <typename Geo>
+__device__ __forceinline__ const uint8_t *enc_g_present(const Geo &geo, uint32_t b) {
+  if constexpr (Geo::MASKED)
+    return geo.present_row(b);
+  else
+    return nullptr;
+}
 struct UniformRecG {
   uint64_t slen, sstride, ostride;
   struct Pre {
@@ -190,6 +219,7 @@ struct RaggedEncG {
   const RaggedItem *items;
   const uint32_t *tile_first;
   int logk;
+  static constexpr bool MASKED = false;
   __device__ __forceinline__ NoPre prepare() const { return {}; }
   __device__ __forceinline__ EncItemG item(NoPre, const uint8_t *payloads, uint8_t *shards, uint32_t b, int) const {
     if (blockIdx.x >= tile_first[b + 1] - tile_first[b]) return {nullptr, nullptr, 0, 0, 0, false};
@@ -233,6 +263,22 @@ __global__ void __launch_bounds__(kBlock) encode_g_ragged(const uint8_t *__restr
                                                           int logk, int logG, uint32_t batch, DevTables t,
                                                           uint2 *scratch) {
   const RaggedEncG geo{items, tile_first, logk};
+  uint32_t *const sig_flag = nullptr;  // (no fused completion signal: never a per-call launch)
+  const uint32_t sig_v = 0;
+#include "enc_g_body.inc"
+}
+
+// the masked form (ec_amd.h ECCR_AMD_encode_missing_batch): only the rows a
+// payload's present row marks missing are written
+__global__ void __launch_bounds__(kBlock) encode_g_missing(const uint8_t *__restrict__ payloads,
+                                                           uint64_t plen, uint64_t pstride,
+                                                           uint8_t *__restrict__ shards, uint64_t slen,
+                                                           uint64_t sstride, int nv, int logn, int logk,
+                                                           int logG, uint32_t batch, DevTables t,
+                                                           uint2 *scratch,
+                                                           const uint8_t *__restrict__ present,
+                                                           const uint32_t *__restrict__ pattern) {
+  const MissingEncG geo{{plen, pstride, slen, sstride}, present, pattern, 1u << logn};
   uint32_t *const sig_flag = nullptr;  // (no fused completion signal: never a per-call launch)
   const uint32_t sig_v = 0;
 #include "enc_g_body.inc"
@@ -581,6 +627,7 @@ const char *kernel_name(Kernel k) {
   case Kernel::X: return #X;
     ECAMD_NAME(encode_k256w) ECAMD_NAME(encode_k256_packed) ECAMD_NAME(encode_kw)
     ECAMD_NAME(encode_k512w) ECAMD_NAME(encode_k1024) ECAMD_NAME(encode_g)
+    ECAMD_NAME(encode_k256w_missing) ECAMD_NAME(encode_g_missing)
     ECAMD_NAME(reconstruct_n1024x) ECAMD_NAME(reconstruct_n1024) ECAMD_NAME(reconstruct_n1024_packed)
     ECAMD_NAME(reconstruct_n4096) ECAMD_NAME(reconstruct_gen) ECAMD_NAME(reconstruct_g)
     ECAMD_NAME(systematic_w) ECAMD_NAME(systematic_g)
@@ -635,6 +682,42 @@ hipError_t launch_encode(const CodeParams &p, const DevTables &t, const EncodeCa
                      ilog2(p.n), ilog2(p.k), ilog2(uint32_t(g.G)), uint32_t(c.batch), t,
                      g.lds ? nullptr : static_cast<uint2 *>(scratch), fuse ? sig->flag : nullptr,
                      fuse ? sig->v : 0u);
+  return hipGetLastError();
+}
+
+// The masked encode's kernel follows the plain encode's choice for the same
+// buffers: the masked two-workgroup kernel where that is encode_k256w, the
+// masked generic kernel (any base, any pitch) everywhere else.
+Kernel choose_encode_missing(const CodeParams &p, const MissingCall &c) {
+  switch (choose_encode(p, c.enc)) {
+    case Kernel::invalid: return Kernel::invalid;
+    case Kernel::encode_k256w: return Kernel::encode_k256w_missing;
+    default: return Kernel::encode_g_missing;
+  }
+}
+
+size_t encode_missing_scratch_bytes(const CodeParams &p, size_t plen, size_t batch) {
+  const size_t plan = k256_applicable(p) && p.n == 1024 ? row_mask_plan_bytes(batch) : 0;
+  const size_t g = generic_scratch_bytes(p.k, shard_len(p.k, plen) / 2, batch);
+  return kTileCounterBytes + (plan > g ? plan : g);
+}
+
+hipError_t launch_encode_missing(const CodeParams &p, const DevTables &t, const MissingCall &c, void *scratch,
+                                 hipStream_t s) {
+  switch (choose_encode_missing(p, c)) {
+    case Kernel::encode_k256w_missing: return launch_encode_k256w_missing(p, t, c, scratch, s);
+    case Kernel::encode_g_missing: break;
+    default: return hipSuccess;  // an empty call
+  }
+  if (!scratch || !c.present) return hipErrorInvalidValue;
+  const EncodeCall &ec = c.enc;
+  const size_t sl = shard_len(p.k, ec.plen);
+  const GenericGeo g = generic_geo(p.k, sl / 2);
+  uint2 *bufs = reinterpret_cast<uint2 *>(static_cast<uint8_t *>(scratch) + kTileCounterBytes);
+  hipLaunchKernelGGL(encode_g_missing, dim3((unsigned)g.tiles, (unsigned)grid_y(ec.batch)), dim3(kBlock), g.shm, s,
+                     ec.payloads, uint64_t(ec.plen), uint64_t(ec.pstride), ec.shards, uint64_t(sl),
+                     uint64_t(ec.sstride), int(p.nv), ilog2(p.n), ilog2(p.k), ilog2(uint32_t(g.G)),
+                     uint32_t(ec.batch), t, g.lds ? nullptr : bufs, c.present, c.pattern);
   return hipGetLastError();
 }
 

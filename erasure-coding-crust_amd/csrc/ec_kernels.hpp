@@ -63,6 +63,14 @@ struct ReconCall {
   uint8_t *out;
   size_t ostride;
 };
+// A masked encode (ECCR_AMD_encode_missing_batch, the second stage of a
+// repair): the encode's record plus the rows to write: payload b writes the
+// rows y < n_validators whose byte in row b of present (row pattern[b]) is 0
+struct MissingCall {
+  EncodeCall enc;
+  const uint8_t *present;
+  const uint32_t *pattern;
+};
 struct SysCall {
   const uint8_t *shards;
   size_t slen, sstride, batch;
@@ -101,6 +109,8 @@ enum class Kernel {
   encode_k512w,
   encode_k1024,
   encode_g,
+  encode_k256w_missing,
+  encode_g_missing,
   reconstruct_n1024x,
   reconstruct_n1024,         // reconstruct_n1024<false>
   reconstruct_n1024_packed,  // reconstruct_n1024<true>
@@ -127,6 +137,27 @@ Kernel choose_reconstruct(const CodeParams &p, const ReconCall &c, const ReconOv
 
 hipError_t launch_encode(const CodeParams &p, const DevTables &t, const EncodeCall &c, void *scratch,
                          hipStream_t s, HostSig *sig = nullptr);
+
+// The masked encode.  choose_encode_missing: a pure host
+// function like choose_encode: encode_k256w_missing exactly where choose_encode
+// picks encode_k256w for the same buffers, encode_g_missing everywhere else
+// (invalid where that is invalid).  Scratch, required (no static schedule):
+// the tile counter's block, then encode_k256w_missing's row-mask plan
+// (n = 1024) or encode_g_missing's transform buffers (generic_scratch_bytes);
+// never 0.  The query cannot see the alignments, so it covers both kernels.
+Kernel choose_encode_missing(const CodeParams &p, const MissingCall &c);
+size_t encode_missing_scratch_bytes(const CodeParams &p, size_t payload_len, size_t batch);
+hipError_t launch_encode_missing(const CodeParams &p, const DevTables &t, const MissingCall &c, void *scratch,
+                                 hipStream_t s);
+hipError_t launch_encode_k256w_missing(const CodeParams &p, const DevTables &t, const MissingCall &c,
+                                       void *scratch, hipStream_t s);
+// the row-mask plan (row_mask.hip): kRowMaskWords words per payload (n =
+// 1024): a 1024-bit mask of the rows to write and a word of phase flags, from
+// the payload's row of d_present (row b, or row d_pattern[b]: no other row is read)
+constexpr uint32_t kRowMaskWords = 33;
+size_t row_mask_plan_bytes(size_t batch);  // a multiple of 256
+hipError_t launch_row_mask_plan(const CodeParams &p, const uint8_t *d_present, const uint32_t *d_pattern,
+                                size_t batch, uint32_t *plan, hipStream_t s);
 
 // Erasure locators (poly_encoder.hpp:90-116, folded form), one workgroup per
 // row of d_present.  d_pattern (nullable): rows b with d_pattern[b] != b are

@@ -8,7 +8,13 @@
 // ec_kernels.hip: prepare(), item(pre, payloads, shards, b, nv) -> EncItemG), payloads, shards,
 // nv, logn, logk, logG, batch, t, scratch, sig_flag, sig_v as encode_g's
 // parameters of these names.
+//
+// A policy with MASKED (encode_g_missing) writes only the rows whose byte in
+// the payload's present row (enc_g_present) is 0, and skips the FFT of a coset
+// none of whose rows is wanted: every `if constexpr (MG)` below, discarded for
+// the other policies.
 {
+  constexpr bool MG = std::decay_t<decltype(geo)>::MASKED;
   extern __shared__ __attribute__((aligned(16))) uint2 smem[];
   const int k = 1 << logk, n = 1 << logn, G = 1 << logG;
   const auto pre = geo.prepare();
@@ -24,6 +30,7 @@
   const uint8_t *P = it.P;
   uint8_t *SH = it.SH;
   const uint64_t plen = it.plen, npieces = it.npieces, sstride = it.sstride;
+  [[maybe_unused]] const uint8_t *const pr = enc_g_present(geo, b);  // MG: the payload's present row
   // BE-unpack 4 pieces per group, zero-padded (poly_encoder.hpp:53-76); the
   // systematic shards are the data symbols themselves (poly_encoder.hpp:239)
   for (int e = threadIdx.x; e < k * G; e += blockDim.x) {
@@ -38,6 +45,9 @@
       xl |= lo << (8 * q);
       xh |= hi << (8 * q);
       if (p < npieces) {
+        if constexpr (MG) {
+          if (i >= nv || pr[i]) continue;
+        }
         SH[uint64_t(i) * sstride + 2 * p] = uint8_t(hi);
         SH[uint64_t(i) * sstride + 2 * p + 1] = uint8_t(lo);
       }
@@ -49,6 +59,11 @@
   for (int e = threadIdx.x; e < k * G; e += blockDim.x) Cf[e] = S[e];
   __syncthreads();
   for (int s = k; s < n && s < nv; s += k) {
+    if constexpr (MG) {  // block-uniform, before the iteration's barriers
+      bool any = false;
+      for (int v = s + int(threadIdx.x); v < s + k && v < nv; v += blockDim.x) any |= pr[v] == 0;
+      if (!__syncthreads_or(any)) continue;
+    }
     if (s > k) {
       for (int e = threadIdx.x; e < k * G; e += blockDim.x) S[e] = Cf[e];
       __syncthreads();
@@ -57,6 +72,9 @@
     for (int e = threadIdx.x; e < k * G; e += blockDim.x) {
       const int g = e & (G - 1), v = s + (e >> logG);
       if (v >= nv) continue;
+      if constexpr (MG) {
+        if (pr[v]) continue;
+      }
       const uint2 x = S[e];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {

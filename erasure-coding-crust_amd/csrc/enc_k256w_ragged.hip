@@ -45,6 +45,7 @@ struct RaggedGeo {
   using Loc = Tile;
   using At = Tile;
   static constexpr uint32_t SLOT_BYTES = 64;  // 12 words
+  static constexpr bool MASKED = false;
   struct Pre {
     uint32_t total;  // tiles of the launch: the plan's last prefix entry
   };

@@ -11,10 +11,16 @@
 //   geo        the geometry policy object (contract: enc_w_common.hpp)
 //   nv, cimg   as encode_k256w's parameters of these names
 // and no other declaration of the names this fragment declares.
+//
+// A policy with MASKED (enc_k256w_missing.hip, which states the schedule) skips
+// the phases its tile's flags leave out and stores under the tile's row mask:
+// every `if constexpr (M)` below.  For the other policies these are discarded
+// and `!M || ...` is true: their code is what it was without them.
 {
   using namespace k256w;
   using Geo = std::decay_t<decltype(geo)>;
   using Tile = typename Geo::Tile;
+  constexpr bool M = Geo::MASKED;
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   const uint32_t tid0 = threadIdx.x;
   auto *slot = reinterpret_cast<LdsWord *>(uintptr_t(SLOT));
@@ -76,11 +82,39 @@
       fetch(geo.loc_or_none(pre, next));
     };
     const auto rsync = [&]() __attribute__((always_inline)) { lds_barrier(); };
+    // M: the tile's phases F (bit 0: systematic rows, bits 1..3: cosets 256,
+    // 512, 768; uniform) and a store phase of theirs.  The ticket is published
+    // behind the systematic stores, as in the uniform kernel, when they and a
+    // coset run; in every other tile right after the tile-start barrier
+    // (`early`: the taken ticket is not kept in a register across a transform).
+    // Coset 768, when it runs, is the last phase whatever else ran: it ends the
+    // tile as the uniform kernel's last coset does (fetch_next in front of its
+    // staging barrier, store_last).  A tile without it ends with tile_end: the
+    // next ticket's read, the next tile's fetch and its State.
+    [[maybe_unused]] const uint32_t F = tile_phases(geo, cur);
+    [[maybe_unused]] const bool early = !(F & 1u) || F == 1u;
+    [[maybe_unused]] const auto store_m = [&](uint32_t s0) __attribute__((always_inline)) {
+      const bool first = !early && s0 == 0;
+      store_rows<Rows>(
+          SH, sstride, s0, nv, piece0, npieces, wave_s, lane,
+          [&]() __attribute__((always_inline)) {
+            if (first && geo.publishes(tid0)) geo.publish(slot, taken, tid0);
+          },
+          tile_mask(geo, cur));
+    };
+    [[maybe_unused]] const auto tile_end = [&]() __attribute__((always_inline)) {
+      if (F == 0) rsync();  // no phase: the barrier between the publication and the read
+      fetch_next();
+      to_state(d, nxt);
+    };
     // store_own's fast path needs 16-B aligned row slices (SH and sstride
     // multiples of 16: the uniform dispatch's alignment test, the ragged
     // contract's shard_off / shard_stride on a 16-B aligned base)
     const auto store = [&](uint32_t s0) __attribute__((always_inline)) {
-      store_rows<Rows>(SH, sstride, s0, nv, piece0, npieces, wave_s, lane, [] {});
+      if constexpr (M)
+        store_m(s0);
+      else
+        store_rows<Rows>(SH, sstride, s0, nv, piece0, npieces, wave_s, lane, [] {});
     };
     // the systematic rows' store phase; the ticket thread 0 took is then
     // published (the wait for the atomic's return then counts only the stores
@@ -92,8 +126,13 @@
     };
     // the last store phase of the tile, then the next tile's State
     const auto store_last = [&](uint32_t s0) __attribute__((always_inline)) {
-      store_rows<Rows>(SH, sstride, s0, nv, piece0, npieces, wave_s, lane,
-                       [&]() __attribute__((always_inline)) { to_state(d, nxt); });
+      if constexpr (M)
+        store_rows<Rows>(
+            SH, sstride, s0, nv, piece0, npieces, wave_s, lane,
+            [&]() __attribute__((always_inline)) { to_state(d, nxt); }, tile_mask(geo, cur));
+      else
+        store_rows<Rows>(SH, sstride, s0, nv, piece0, npieces, wave_s, lane,
+                         [&]() __attribute__((always_inline)) { to_state(d, nxt); });
     };
 
     // A wave none of whose 8 pieces exist (the last, partial tile of a payload:
@@ -103,19 +142,27 @@
     // branch).  Wave 0 never idles: a tile's first piece exists.
     if (piece0 + 8 * wave_s >= npieces) {
       rsync();  // tile start
-      rsync();  // systematic rows staged
-      store(0);
-      rsync();  // after IFFT pass A
+      if (!M || (F & 1u)) {
+        rsync();  // systematic rows staged
+        store(0);
+      }
+      if (!M || (F & 0xEu)) rsync();  // after IFFT pass A
       for (uint32_t sh = K; sh < 1024u && int(sh) < nv; sh += K) {
+        if constexpr (M) {
+          if (!(F & (1u << (sh >> 8)))) continue;
+        }
         rsync();  // after pass C
         rsync();  // rows staged
-        if (sh == last_sh) {
+        if (M ? sh == 3 * K : sh == last_sh) {
           fetch_next();
           store_last(sh);
         } else {
           store(sh);
         }
         __builtin_amdgcn_sched_barrier(0);
+      }
+      if constexpr (M) {
+        if (!(F & 8u)) tile_end();
       }
       cur = next;
       continue;
@@ -126,24 +173,35 @@
 
     // ---- systematic shards 0..255 = the data symbols (poly_encoder.hpp:239)
     rsync();  // the other waves are done reading this region (last tile)
-    stage_own8(s, xch, q, inst, wave);
-    rsync();
-    store_sys();
-    __builtin_amdgcn_sched_barrier(0);
-    {  // into tower coordinates
-      const TowerK tk = tower_k();
-#pragma unroll
-      for (int r = 0; r < 8; ++r) s.l[r] = tower_lo(s.l[r], s.h[r], tk);
+    if constexpr (M) {
+      if (early && geo.publishes(tid0)) geo.publish(slot, taken, tid0);
     }
+    if (!M || (F & 1u)) {
+      stage_own8(s, xch, q, inst, wave);
+      rsync();
+      if constexpr (M)
+        store(0);
+      else
+        store_sys();
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    State coef;
+    if (!M || (F & 0xEu)) {
+      {  // into tower coordinates
+        const TowerK tk = tower_k();
+#pragma unroll
+        for (int r = 0; r < 8; ++r) s.l[r] = tower_lo(s.l[r], s.h[r], tk);
+      }
 
-    // ---- IFFT_256 (index 0): passes A (bits 0-2), B (3-5), C (6-7)
-    ipass<0>(s, posA(q, 0));
-    rsync();  // systematic rows read out of the regions
-    exchange<LA, LB>(s, xch, xb);
-    ipass<3>(s, posB(q, 0));
-    exchange<LB, LC>(s, xch, xb);
-    ipassC(s);
-    State coef = s;
+      // ---- IFFT_256 (index 0): passes A (bits 0-2), B (3-5), C (6-7)
+      ipass<0>(s, posA(q, 0));
+      rsync();  // systematic rows read out of the regions
+      exchange<LA, LB>(s, xch, xb);
+      ipass<3>(s, posB(q, 0));
+      exchange<LB, LC>(s, xch, xb);
+      ipassC(s);
+      coef = s;
+    }
 
     // ---- FFT_256 at each coset shift (encodeLow, poly_encoder.hpp:229-237).
     // Kinds of pass A's stages 2 / 1 / 0 by coset: 256: sub / sub / F9;
@@ -175,11 +233,21 @@
         store(off);
       __builtin_amdgcn_sched_barrier(0);
     };
-    // n_validators 766..1024 (k = 256, n = 1024): cosets 256, 512 and, above
-    // 768, 768; the last one has its own body (it fetches the next tile)
-    coset(SubTab(), F9Tab(), K, std::false_type());
-    if (last_sh == 3 * K) coset(F9Tab(), Tab(), 2 * K, std::false_type());
-    coset(F9Tab(), Tab(), last_sh, std::true_type());
+    if constexpr (M) {
+      // the wanted cosets (the plan sets no bit of a coset at or above nv)
+      if (F & 2u) coset(SubTab(), F9Tab(), K, std::false_type());
+      if (F & 4u) coset(F9Tab(), Tab(), 2 * K, std::false_type());
+      if (F & 8u)
+        coset(F9Tab(), Tab(), 3 * K, std::true_type());
+      else
+        tile_end();
+    } else {
+      // n_validators 766..1024 (k = 256, n = 1024): cosets 256, 512 and, above
+      // 768, 768; the last one has its own body (it fetches the next tile)
+      coset(SubTab(), F9Tab(), K, std::false_type());
+      if (last_sh == 3 * K) coset(F9Tab(), Tab(), 2 * K, std::false_type());
+      coset(F9Tab(), Tab(), last_sh, std::true_type());
+    }
     cur = next;
   }
 }

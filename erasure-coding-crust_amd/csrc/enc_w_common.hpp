@@ -256,6 +256,19 @@ __device__ __forceinline__ void to_state(const v4u (&d)[4], State &s) {
 struct RowLane {
   uint32_t v0, c, a;
 };
+// Which rows of a store phase are written: every row (the encodes), or the rows
+// whose bit is set in a 1024-bit mask in LDS (word y >> 5, bit y & 31: the
+// masked encode, enc_k256w_missing.hip).  MASKED false compiles to nothing.
+struct AllRows {
+  static constexpr bool MASKED = false;
+};
+struct LdsRowMask {
+  static constexpr bool MASKED = true;
+  uint32_t base;  // LDS address of the mask's word 0
+  __device__ __forceinline__ bool wanted(uint32_t row) const {
+    return (lds_r32(base + ((row >> 5) << 2)) >> (row & 31)) & 1u;
+  }
+};
 template <typename G>
 __device__ __forceinline__ bool store_fast(const uint8_t *SH, uint64_t sstride, uint32_t s0, int nv,
                                            uint64_t piece0, uint64_t npieces) {
@@ -266,10 +279,10 @@ __device__ __forceinline__ bool store_fast(const uint8_t *SH, uint64_t sstride, 
 // `then` runs at the end of each path: code that waits for a load issued
 // before the stores is placed there, so the compiler's wait on the fast path
 // counts its 4 stores (vmcnt(4)) instead of the minimum over every path.
-template <typename G, typename Then>
+template <typename G, typename Then, typename Mask = AllRows>
 __device__ __forceinline__ void store_own(uint8_t *SH, uint64_t sstride, uint32_t s0, int nv,
                                           uint64_t piece0, uint64_t npieces, uint32_t wave,
-                                          uint32_t lane, Then &&then) {
+                                          uint32_t lane, Then &&then, Mask mask = {}) {
   static_assert(G::K == 4 * G::VSTEP, "4 stores per lane: the vmcnt(4) waits count them");
   asm volatile("" : "+v"(lane));  // recomputed here, not kept live across the FFTs
   const RowLane rl = G::lane_role(wave, lane);
@@ -280,6 +293,9 @@ __device__ __forceinline__ void store_own(uint8_t *SH, uint64_t sstride, uint32_
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       const v4u val = G::read(a, it);
+      if constexpr (Mask::MASKED) {
+        if (!mask.wanted(s0 + uint32_t(it) * G::VSTEP + v0)) continue;
+      }
       __builtin_nontemporal_store(val, reinterpret_cast<v4u *>(dst + it * dstep));  // written once
     }
     then();
@@ -294,6 +310,9 @@ __device__ __forceinline__ void store_own(uint8_t *SH, uint64_t sstride, uint32_
     const auto raw = G::read(a, it);  // a v4u only below: not assembled for rows that are cut
     const uint32_t shard = s0 + v;
     if (int(shard) >= nv) continue;
+    if constexpr (Mask::MASKED) {
+      if (!mask.wanted(shard)) continue;
+    }
     uint8_t *dst = SH + uint64_t(shard) * sstride + 2 * p;
     const v4u val = raw;
     if (p + 8 <= npieces) {
@@ -314,11 +333,12 @@ __device__ __forceinline__ void store_own(uint8_t *SH, uint64_t sstride, uint32_
 }
 
 // a store phase: the row stores (LDS reads + global stores) at raised issue priority
-template <typename G, typename Then>
+template <typename G, typename Then, typename Mask = AllRows>
 __device__ __forceinline__ void store_rows(uint8_t *SH, uint64_t sstride, uint32_t s0, int nv, uint64_t piece0,
-                                           uint64_t npieces, uint32_t wave, uint32_t lane, Then &&then) {
+                                           uint64_t npieces, uint32_t wave, uint32_t lane, Then &&then,
+                                           Mask mask = {}) {
   __builtin_amdgcn_s_setprio(1);
-  store_own<G>(SH, sstride, s0, nv, piece0, npieces, wave, lane, then);
+  store_own<G>(SH, sstride, s0, nv, piece0, npieces, wave, lane, then, mask);
   __builtin_amdgcn_s_setprio(0);
 }
 
@@ -350,6 +370,11 @@ __device__ __forceinline__ void store_rows(uint8_t *SH, uint64_t sstride, uint32
 //   fetch(pre, Loc)      the payload fetch's geometry (Fetch)
 //   At, at(pre, T), piece0(At), rows(At), npieces(pre, T), sstride(T)
 //                        geometry of a valid tile's transforms and stores
+//   MASKED               false: every phase of a tile runs and every row is
+//                        stored.  true (enc_k256w_missing.hip, which states the
+//                        schedule of a tile with skipped phases): also
+//                        phases(T), row_mask(T), read through tile_phases /
+//                        tile_mask below
 //
 // The ticket protocol.  Tiles come from the launch's counter (zeroed before the
 // launch), so the two workgroups of a CU, which the issue arbiter serves at
@@ -389,6 +414,7 @@ struct UniformGeo {
   uint32_t *tick;
   using Tile = uint32_t;  // the ticket itself
   static constexpr uint32_t SLOT_BYTES = 16;
+  static constexpr bool MASKED = false;
   struct Pre {  // per launch: pieces and tiles per payload, tiles of the launch
     uint64_t npieces;
     uint32_t tiles_pp, total;
@@ -432,6 +458,25 @@ struct UniformGeo {
   __device__ __forceinline__ uint64_t sstride(Tile) const { return sstride_; }
   __device__ __forceinline__ uint8_t *rows(At a) const { return shards + a.b * uint64_t(nv) * sstride_; }
 };
+
+// What a tile loop asks a MASKED policy, in a form that compiles for every
+// policy (the loops are textual fragments inside non-template kernels): the
+// tile's phase flags (bit 0: the systematic rows, bits 1..3: the cosets 256,
+// 512, 768) and its row mask.
+template <typename Geo>
+__device__ __forceinline__ uint32_t tile_phases(const Geo &geo, const typename Geo::Tile &t) {
+  if constexpr (Geo::MASKED)
+    return geo.phases(t);
+  else
+    return 0xFu;
+}
+template <typename Geo>
+__device__ __forceinline__ auto tile_mask(const Geo &geo, const typename Geo::Tile &t) {
+  if constexpr (Geo::MASKED)
+    return geo.row_mask(t);
+  else
+    return AllRows{};
+}
 
 }  // namespace
 

@@ -139,6 +139,15 @@ def lib():
             "ECCR_AMD_error_locator_ws": (NPRSResult, [ul, vp, ul, vp, vp, ul, vp]),
             "ECCR_AMD_reconstruct_batch_ws": (NPRSResult, [ul, vp, ul, ul, vp, vp, vp, ul, vp, ul,
                                                            vp, ul, vp]),
+            "ECCR_AMD_encode_missing_batch": (NPRSResult, [ul, vp, ul, ul, ul, vp, ul, vp, vp, vp]),
+            "ECCR_AMD_encode_missing_batch_ws": (NPRSResult, [ul, vp, ul, ul, ul, vp, ul, vp, vp, vp, ul,
+                                                              vp]),
+            "ECCR_AMD_encode_missing_workspace_bytes": (ul, [ul, ul, ul]),
+            "ECCR_AMD_encode_missing_kernel": (C.c_char_p, [ul, vp, ul, ul, ul, vp, ul]),
+            "ECCR_AMD_repair_batch": (NPRSResult, [ul, vp, ul, ul, vp, vp, vp, ul, vp, ul, vp]),
+            "ECCR_AMD_repair_batch_ws": (NPRSResult, [ul, vp, ul, ul, vp, vp, vp, ul, vp, ul, vp, ul,
+                                                      vp]),
+            "ECCR_AMD_repair_workspace_bytes": (ul, [ul, ul, ul]),
             "ECCR_AMD_encode_ragged": (NPRSResult, [ul, vp, vp, ul, ul, vp, vp, vp]),
             "ECCR_AMD_encode_ragged_ws": (NPRSResult, [ul, vp, vp, ul, ul, vp, vp, vp, ul, vp]),
             "ECCR_AMD_reconstruct_ragged": (NPRSResult, [ul, vp, vp, vp, vp, vp, ul, ul, vp, vp, vp]),
@@ -397,6 +406,63 @@ def reconstruct_kernel(nv, d_shards, shard_len_, shard_stride, d_present, d_err_
                                           _p(d_present), _p(d_err_log), batch, _p(d_out),
                                           out_stride)
     return None if r is None else r.decode()
+
+
+def _opt_p(x):
+    return None if x is None else _p(x)
+
+
+def encode_missing_batch(nv, d_payloads, payload_len, payload_stride, batch, d_shards, shard_stride,
+                         d_present, d_pattern=None, stream=None):
+    """encode_batch that writes only the rows y < nv whose byte in payload b's present row (row b of
+    d_present, or row d_pattern[b]) is 0; no other byte of d_shards is written (ec_amd.h)."""
+    _check(lib().ECCR_AMD_encode_missing_batch(
+        nv, _p(d_payloads), payload_len, payload_stride, batch, _p(d_shards), shard_stride,
+        _opt_p(d_present), _opt_p(d_pattern), _stream(stream)), "encode_missing_batch")
+
+
+def encode_missing_batch_ws(nv, d_payloads, payload_len, payload_stride, batch, d_shards,
+                            shard_stride, d_present, ws, d_pattern=None, stream=None):
+    """encode_missing_batch on caller-owned scratch `ws` (graph-capture-safe after one warm call)."""
+    wp, wb = _ws(ws)
+    _check(lib().ECCR_AMD_encode_missing_batch_ws(
+        nv, _p(d_payloads), payload_len, payload_stride, batch, _p(d_shards), shard_stride,
+        _opt_p(d_present), _opt_p(d_pattern), wp, wb, _stream(stream)), "encode_missing_batch_ws")
+
+
+def encode_missing_workspace_bytes(nv, payload_len, batch):
+    return int(lib().ECCR_AMD_encode_missing_workspace_bytes(nv, payload_len, batch))
+
+
+def encode_missing_kernel(nv, d_payloads, payload_len, payload_stride, batch, d_shards, shard_stride):
+    """Name of the kernel encode_missing_batch would launch for these arguments, or None
+    (host-only, as encode_kernel)."""
+    r = lib().ECCR_AMD_encode_missing_kernel(nv, _p(d_payloads), payload_len, payload_stride,
+                                             batch, _p(d_shards), shard_stride)
+    return None if r is None else r.decode()
+
+
+def repair_batch(nv, d_shards, shard_len_, shard_stride, d_present, d_err_log, batch, d_out,
+                 out_stride, d_pattern=None, stream=None):
+    """In place: reconstruct the payloads into d_out as reconstruct_batch does, then write the
+    missing rows of d_shards from them; present rows are read and never written (ec_amd.h)."""
+    _check(lib().ECCR_AMD_repair_batch(
+        nv, _opt_p(d_shards), shard_len_, shard_stride, _opt_p(d_present), _opt_p(d_err_log),
+        _opt_p(d_pattern), batch, _opt_p(d_out), out_stride, _stream(stream)), "repair_batch")
+
+
+def repair_batch_ws(nv, d_shards, shard_len_, shard_stride, d_present, d_err_log, batch, d_out,
+                    out_stride, ws, d_pattern=None, stream=None):
+    """repair_batch on caller-owned scratch `ws` (graph-capture-safe after one warm call)."""
+    wp, wb = _ws(ws)
+    _check(lib().ECCR_AMD_repair_batch_ws(
+        nv, _opt_p(d_shards), shard_len_, shard_stride, _opt_p(d_present), _opt_p(d_err_log),
+        _opt_p(d_pattern), batch, _opt_p(d_out), out_stride, wp, wb, _stream(stream)),
+        "repair_batch_ws")
+
+
+def repair_workspace_bytes(nv, shard_len_, batch):
+    return int(lib().ECCR_AMD_repair_workspace_bytes(nv, shard_len_, batch))
 
 
 def reconstruct_n1024x_waves(shard_len_: int) -> int:

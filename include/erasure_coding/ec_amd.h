@@ -369,6 +369,93 @@ unsigned long ECCR_AMD_systematic_ragged_workspace_bytes(unsigned long n_validat
                                                          unsigned long max_shard_len);
 const char *ECCR_AMD_systematic_ragged_kernel(unsigned long n_validators);
 
+/* ---- repair: regenerate only the missing rows -------------------------------
+ * The other half of the codec: from any k present rows the reconstruct gives
+ * the payload back; these calls give the missing ROWS back, and only those.
+ *
+ * ECCR_AMD_encode_missing_batch is the encode under a row mask: it writes the
+ * rows y < n_validators of payload b whose byte in its present row (row b of
+ * d_present, or row d_pattern[b]; layouts as in ECCR_AMD_reconstruct_batch_ws)
+ * is 0.  As there, only the rows the payloads name are read: with d_pattern,
+ * d_present (and a repair's d_err_log) may hold fewer rows than the batch, for
+ * instance ONE row for every payload.  No other byte of d_shards is written: not a present row, not the
+ * bytes between shard_len and shard_stride, not a row at or above
+ * n_validators whatever its present byte.  d_shards is never read.  A caller
+ * that wants one validator's chunk marks every other row present.
+ *
+ * ECCR_AMD_repair_batch works in place on a damaged set: it reconstructs the
+ * payloads into d_out exactly as ECCR_AMD_reconstruct_batch_ws does (d_err_log
+ * from ECCR_AMD_error_locator), then writes the missing rows of d_shards from
+ * them (the masked encode with payload_len = shard_len * k and pitch
+ * out_stride).  Present rows are read and never written.  d_out is required:
+ * the payload is a product of the call.  It must not overlap d_shards (not
+ * checked).  With fewer than k present rows the bytes of d_out and of the
+ * missing rows are unspecified, and nothing outside them is touched; the
+ * device path does not count, as the reconstruct's.
+ *
+ * Validation.  A NULL buffer (d_pattern excepted) is BAD_PAYLOAD with an
+ * ECCR_AMD_last_error text; then the encode's tests (BAD_PAYLOAD) for the
+ * masked encode, the reconstruct's (UNEVEN_LENGTH, NON_UNIFORM_CHUNKS; a
+ * shard_len of 0: BAD_PAYLOAD) for the repair.  An empty batch is OK and does
+ * nothing.
+ *
+ * Workspace.  Both calls always need device scratch: the tile counter, the
+ * masked encode's row-mask plan (132 bytes per payload at
+ * n_validators 766 .. 1024) or the generic kernel's transform buffers, and
+ * for the repair the reconstruct's.  The plain calls take it from the scratch
+ * private to (device, stream), as every plain call does.  The _ws forms take
+ * the caller's: 256-B aligned, at least the queried size; a NULL, short or
+ * misaligned workspace is UNKNOWN_CODE_PARAM (masked encode) /
+ * UNKNOWN_RECONSTRUCTION (repair) with nothing launched and the device not
+ * touched: there is no static-schedule fallback.  The two stages of a repair
+ * run one after the other on the stream and SHARE the workspace:
+ * ECCR_AMD_repair_workspace_bytes is the larger of the two stages' needs, not
+ * their sum.  The queries are never 0 for valid parameters, monotone in
+ * batch, and 0 for invalid ones (n_validators, an empty batch, a payload_len
+ * of 0; for the repair an odd or zero shard_len).  After one warm call the
+ * _ws forms can be captured into a hipGraph: every word of the plan is
+ * rebuilt and the tile counter zeroed by kernels on each replay, so
+ * d_present and d_err_log may change between replays.
+ *
+ * Kernels.  Where ECCR_AMD_encode_kernel names encode_k256w for the same
+ * buffers (n_validators 766 .. 1024, at least 128 pieces of 512 bytes per
+ * payload, the alignments of the fast encode), the masked encode runs
+ * encode_k256w_missing, which skips the transforms of a coset none of whose
+ * rows is wanted; everywhere else it runs encode_g_missing, the generic
+ * kernel under the same mask: correct, and slow.
+ * ECCR_AMD_encode_missing_kernel names the choice (host-only, as
+ * ECCR_AMD_encode_kernel; NULL where nothing would be launched). */
+struct NPRSResult ECCR_AMD_encode_missing_batch(unsigned long n_validators, const uint8_t *d_payloads,
+                                                unsigned long payload_len, unsigned long payload_stride,
+                                                unsigned long batch, uint8_t *d_shards,
+                                                unsigned long shard_stride, const uint8_t *d_present,
+                                                const uint32_t *d_pattern, void *stream);
+struct NPRSResult ECCR_AMD_encode_missing_batch_ws(unsigned long n_validators, const uint8_t *d_payloads,
+                                                   unsigned long payload_len, unsigned long payload_stride,
+                                                   unsigned long batch, uint8_t *d_shards,
+                                                   unsigned long shard_stride, const uint8_t *d_present,
+                                                   const uint32_t *d_pattern, void *d_workspace,
+                                                   unsigned long workspace_bytes, void *stream);
+unsigned long ECCR_AMD_encode_missing_workspace_bytes(unsigned long n_validators, unsigned long payload_len,
+                                                      unsigned long batch);
+const char *ECCR_AMD_encode_missing_kernel(unsigned long n_validators, const uint8_t *d_payloads,
+                                           unsigned long payload_len, unsigned long payload_stride,
+                                           unsigned long batch, const uint8_t *d_shards,
+                                           unsigned long shard_stride);
+struct NPRSResult ECCR_AMD_repair_batch(unsigned long n_validators, uint8_t *d_shards, unsigned long shard_len,
+                                        unsigned long shard_stride, const uint8_t *d_present,
+                                        const uint16_t *d_err_log, const uint32_t *d_pattern,
+                                        unsigned long batch, uint8_t *d_out, unsigned long out_stride,
+                                        void *stream);
+struct NPRSResult ECCR_AMD_repair_batch_ws(unsigned long n_validators, uint8_t *d_shards,
+                                           unsigned long shard_len, unsigned long shard_stride,
+                                           const uint8_t *d_present, const uint16_t *d_err_log,
+                                           const uint32_t *d_pattern, unsigned long batch, uint8_t *d_out,
+                                           unsigned long out_stride, void *d_workspace,
+                                           unsigned long workspace_bytes, void *stream);
+unsigned long ECCR_AMD_repair_workspace_bytes(unsigned long n_validators, unsigned long shard_len,
+                                              unsigned long batch);
+
 /* ---- host-resident batches --------------------------
  * Stream a host batch through the device in chunks of `chunk` payloads (0 =
  * automatic: ~16 MB over the link per chunk), three chunks in flight (H2D /

@@ -124,15 +124,16 @@ for k in kinds:
         counter_bytes = max(counter_bytes, 1152)
     elif k == "nbread":
         for old in ("    rsync();  // the other waves are done reading this region (last tile)\n",
-                    "    rsync();  // systematic rows read out of the regions\n",
+                    "      rsync();  // systematic rows read out of the regions\n",
                     "      rsync();  // previous coset's rows read out\n",
-                    "      rsync();  // tile start\n", "      rsync();  // after IFFT pass A\n",
+                    "      rsync();  // tile start\n",
+                    "      if (!M || (F & 0xEu)) rsync();  // after IFFT pass A\n",
                     "        rsync();  // after pass C\n"):
             enc = rep(enc, old, "")
     elif k == "nbstg":
-        for old, new in (("    rsync();\n    store_sys();", "    store_sys();"),
+        for old, new in (("      rsync();\n      if constexpr (M)\n        store(0);", "      if constexpr (M)\n        store(0);"),
                          ("      rsync();\n      if constexpr (decltype(last)::value)", "      if constexpr (decltype(last)::value)"),
-                         ("      rsync();  // systematic rows staged\n", ""),
+                         ("        rsync();  // systematic rows staged\n", ""),
                          ("        rsync();  // rows staged\n", "")):
             enc = rep(enc, old, new)
     elif k == "nost":
